@@ -41,6 +41,12 @@ Timing.  After W warmup steps:
     schedule (``--streams`` launches of ``--many`` batches in flight) between ONE pair of HIP events (no gate, no per-region synchronisation):
     the rate at seconds, with the shader / memory clocks read from rocm-smi before and after.
 
+``--dump-outputs DIR`` writes what the contract region's last step computed, as a caller of the path receives it for that
+batch: ``onehot`` on a fixed, seeded sample of its rows (``sample_rows``), ``out_offsets``, and ``haps`` with ``--haps``, as
+``DIR/<name>.npy`` in float32 / float64 (under 64 MB).  That step's launch writes an output set no other launch writes (the
+rotating ones are shared by launches on free-running streams).  Dataset and batches are seeded, so two builds run with the
+same arguments can be compared output for output.
+
 For N > 1 the driver launches one rank per GPU (torch.distributed.run); rows are independent,
 so each rank processes its own 4096-window batches (weak scaling, no data-path collective)
 and ``value`` = windows all ranks processed / max-over-ranks time.  ``--strong`` splits ONE
@@ -691,7 +697,13 @@ def main() -> None:
                     help="gvl_set_tuning before anything is launched (A/B runs): pipe_rows_x100, pipe_min_rows, lean_sub, track_plan_max_mb, ragged_sizing")
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the short ragged-cfg3 and cfg4 legs of the default run (N = 1 only; `secondary` in the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last of the K timed steps computed (rank 0's batch) as DIR/<name>.npy, float32 / float64")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.cpu_only or args.workload == "cfg4"):
+        ap.error("--dump-outputs covers the GPU haplotype path (cfg1-cfg3), not --cpu-only or cfg4")
 
     if args.cpu_only:
         cpu_only(args)
@@ -877,21 +889,64 @@ def main() -> None:
             st_.prebuild((G, steps % G))
     flush = getattr(step_pipelined, "flush", lambda: None)
 
+    def own_last_step():
+        """--dump-outputs: the contract region's last step as step_pipelined would issue it -- the same batches, launch and stream --
+        but into an output set of its own (vslots, as the sustained leg's last launch): the rotating slots are shared by launches on
+        free-running streams, and an earlier one can still be writing the last one's.  Arguments built here, before the clock starts.
+        -> (launch(i) for step i = steps - 1, the ReconOutput it writes)"""
+        if G > 1:
+            size, g_last = steps % G or G, step_pipelined.g + (steps - 1) // G
+            key = step_pipelined.key(g_last, size)
+            p_ = dev.pack_many([batches[(key[0] * G + i_) % n_rot] for i_ in range(size)], [vslots[i_][1] for i_ in range(size)])
+
+            def launch(i):
+                assert step_pipelined.g == g_last and step_pipelined.pending == size - 1
+                if _many(_dref, p_[0], p_[1], p_[2], step_pipelined.sp[g_last % len(step_pipelined.sp)]):
+                    raise RuntimeError("gvl_reconstruct_many failed")
+                step_pipelined.g, step_pipelined.pending = g_last + 1, 0
+            return launch, vslots[size - 1][0]
+        own = _C.byref(vslots[0][1])
+
+        def launch(i):
+            j = counter[0]
+            counter[0] += 1
+            if _fn(_dref, _bref[j % n_rot], own, _sptr[i % len(streams)]):
+                raise RuntimeError("gvl_reconstruct failed")
+        return launch, vslots[0][0]
+
+    def host_outputs(out) -> dict:
+        """What a caller of the timed path receives for one batch, on the host as float arrays: the one-hot (and the haplotype bytes
+        with --haps) of a fixed, seeded sample of its rows -- all of them would be 134 MB of float32 at 4096 x 2048 --, the sampled
+        row indices, and the row offsets."""
+        n = min(K, max(1, (48 << 20) // (L * (16 + (4 if args.haps else 0)))))
+        rows = np.sort(np.random.default_rng(0).choice(K, n, replace=False))
+        idx = torch.from_numpy(rows).to(out.onehot.device)
+        res = {"onehot": out.onehot.view(K, L, 4).index_select(0, idx).cpu().numpy().astype(np.float32),
+               "sample_rows": rows.astype(np.float64),
+               "out_offsets": out.out_offsets.cpu().numpy().astype(np.float64)}
+        if args.haps:
+            res["haps"] = out.haps.view(K, L).index_select(0, idx).cpu().numpy().astype(np.float32)
+        return res
+
     # ---- warmup, then the contract region: EXACTLY K steps between barrier + synchronize ----
     for i in range(args.warmup):
         step_pipelined(i)
     flush()
+    last_step, last_out = own_last_step() if args.dump_outputs and rank == 0 else (step_pipelined, None)
     torch.cuda.synchronize()
     tm.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for i in range(steps):
+    for i in range(steps - 1):
         step_pipelined(i)
+    last_step(steps - 1)
     flush()
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     tm.barrier()
     wall = tm.allmax([t1 - t0])[0]
+    # (read now: the sustained leg and `verified` below write vslots too)
+    dump = host_outputs(last_out) if last_out is not None else None
 
     # ---- the same region repeated; GPU time per region from HIP events ---------------------
     region_ms, n_regions, spans = tm.measure(step_pipelined, steps, streams)
@@ -1359,6 +1414,12 @@ def main() -> None:
             res["gather_bytes_per_rank"] = K * L * 4
         if world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(ds.host_static(), ds.host_batch(qsets[0], rc=rc_on), args.cpu_budget)
+        if dump is not None:
+            out_dir = Path(args.dump_outputs)
+            out_dir.mkdir(parents=True, exist_ok=True)
+            assert sum(a.nbytes for a in dump.values()) <= 64_000_000
+            for name, a in dump.items():
+                np.save(out_dir / f"{name}.npy", a)
         print(json.dumps(res), flush=True)
 
     if dist is not None:

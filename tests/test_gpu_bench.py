@@ -9,6 +9,7 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -83,6 +84,33 @@ def test_bench_secondary_legs():
         assert "error" not in leg, (name, leg)
         assert leg["ms_per_step"] > 0 and 0 < leg["step_frac"] < 1.3 and leg["algorithmic_bytes_per_step"] > 4096 * 2048 * 4, (name, leg)
     assert sec["random_shifts"]["deterministic_ms_per_step"] > 0
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR: the last timed step's outputs as float .npy files under 64 MB, the same from run to run with the same
+    arguments.  With --rotate 8, the last of 7 steps after 3 warmup steps in launches of 16 batches is batch 6 -- as is the
+    last of 7 steps without warmup at one launch per batch -- so the two kernel paths must dump the same arrays."""
+    quick = [*SMALL, "--no-cpu-baseline", "--no-hot", "--sustained-s", "0"]
+    runs = {"a": ["--steps", "7", "--warmup", "3"], "b": ["--steps", "7", "--warmup", "3"],
+            "single": ["--steps", "7", "--warmup", "0", "--many", "1"]}
+    got = {}
+    for name, extra in runs.items():
+        d = _run([sys.executable, "bench.py", "--gpus", "1", *extra, *quick, "--dump-outputs", str(tmp_path / name)])
+        assert d["steps"] == 7
+        files = sorted(tmp_path.joinpath(name).glob("*.npy"))
+        assert [f.stem for f in files] == ["onehot", "out_offsets", "sample_rows"]
+        got[name] = {f.stem: np.load(f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in got[name].values())
+        assert sum(f.stat().st_size for f in files) <= 64_000_000
+    a = got["a"]
+    K, L = 4096, 2048
+    rows = a["sample_rows"].astype(np.int64)
+    assert len(rows) == len(np.unique(rows)) == a["onehot"].shape[0] and 0 <= rows.min() and rows.max() < K
+    assert a["onehot"].shape[1:] == (L, 4) and set(np.unique(a["onehot"])) <= {0.0, 1.0} and a["onehot"].sum(-1).max() == 1
+    np.testing.assert_array_equal(a["out_offsets"], np.arange(K + 1) * L)
+    for other in ("b", "single"):
+        for k in a:
+            np.testing.assert_array_equal(a[k], got[other][k], err_msg=f"{other}: {k}")
 
 
 @pytest.mark.parametrize("extra", [["--gather"], ["--strong", "--gather"]], ids=["weak+gather", "strong+gather"])
