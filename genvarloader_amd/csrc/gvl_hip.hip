@@ -338,32 +338,8 @@ int pick_chunk(i64 max_len, int *chunks, int *chunk_len) {
     return 0;
 }
 
-// GVL_DBG (read once; gvl_set_debug_flags overrides it): test/diagnostic switches that remove
-// one way a row can reach its output, so that the GPU suite can be run down every path:
-//     8  every row through the scalar walk (haplotypes and tracks)
-//    32  no scan-free plan for SNP-only rows (they join the packed plan)
-//   256  a mixed ragged launch's long rows by the wave that meets them, chunk after chunk (no front workgroups: lean_solo_rows' crews)
-//   512  no packable rows at all (every row runs the per-wave scans)
-//    16  ignore gvl_static.geno_rec (records come from geno_v_idxs -> vrec)
-//    64  ignore gvl_static.slot_rec (rows find their records through the CSR)
-//   128  no speculative reference reads in front of the plan
-//  1024  painter ignores the per-list bucket index (exact 64-ary searches per chunk)
-//  2048  length deltas (get_diffs_sparse, ragged sizing) always one wave per row
-//  8192  painter always paints an LDS image (no start-bitmap lookup for non-overlapping candidates)
-// 16384  no lean kernel (the all-purpose kernel over every row, as before round 3)
-// 32768  the lean kernel hands EVERY row to its solo general path (per-wave scans from the byte reference)
-// 131072 the native loop sizes the scratch tracks per batch (not once per epoch)
-// 262144 / 524288  [-DGVL_DIAG builds only; masked off otherwise] timing ablations of the lean kernel (WRONG output for rows with
-//        indels): no re-alignment / allele bytes (phases A and B as for a SNP-only row); no scan plan either
-// 65536  the lean kernel re-reads the runs of a row with indels from memory (never re-aligns the speculative window in LDS)
-// 1048576 rows longer than one chunk never take the lean kernel (LONG): the all-purpose kernel as before
-// 2097152 realignment from intervals never uses its window (every value looked up in the interval list itself)
-// 4194304 tracks are always painted into the scratch track first (no realignment straight from the intervals)
-// 8388608 / 16777216  [-DGVL_DIAG builds only] timing ablations of realign_tracks_kernel (NO output): stop behind the walk / behind the window build
-// 1073741824 round 4's routing of the other output modes: channel-major one-hot, keep masks, annotations and get_reference run the
-//        all-purpose kernel (their lean forms are this round's)
-// 536870912 rows of several chunks go without chunk plans (hap_plan_kernel): every chunk-wave of the lean kernel walks its row itself
-// and 1 / 2 / 4 = timing ablations (no variants / no stores / no loads) [-DGVL_DIAG builds only].
+// GVL_DBG (read once; gvl_set_debug_flags overrides it): the bits are DbgBit, gvl_internal.inc.  Each C-ABI entry point reads it
+// once and passes the value down (ReconArgs::dbg, TrackArgs::dbg); the native loop snapshots it per epoch table (LoaderKnobs).
 // (written by gvl_set_debug_flags on one thread while the loader's producer thread reads it: a relaxed atomic)
 int g_debug_override = -1;
 int debug_flags() {
@@ -420,10 +396,9 @@ template <typename F> hipError_t traced(const char *tag, F f) {
     return e;
 }
 
-// rows with many variants (mean > 16 per genotype slot, or GVL_DBG=2048): one wave per row instead of one lane
-static bool diffs_long_rows(const gvl_static *st) {
-    if (debug_flags() & 2048) return true;
-    return st->n_geno_offsets > 0 && st->n_geno / st->n_geno_offsets > 16;
+// rows with many variants (mean > 16 per genotype slot, or DBG_DIFFS_WAVE_ROWS): one wave per row instead of one lane
+static bool diffs_long_rows(const gvl_static *st, int dbg) {
+    return (dbg & DBG_DIFFS_WAVE_ROWS) || (st->n_geno_offsets > 0 && st->n_geno / st->n_geno_offsets > 16);
 }
 
 int fill_diff_args(DiffArgs &D, const gvl_static *st, const gvl_batch *bt, const char *who) {
@@ -433,7 +408,7 @@ int fill_diff_args(DiffArgs &D, const gvl_static *st, const gvl_batch *bt, const
     D.geno_offset_idx = (const i64 *)bt->geno_offset_idx; D.n_rows = bt->batch * bt->ploidy;
     D.ploidy = (int)bt->ploidy;
     D.geno_v_idxs = st->geno_v_idxs; D.go_starts = (const i64 *)st->geno_o_starts;
-    D.grec = (debug_flags() & 16) ? nullptr : st->geno_rec;
+    D.grec = (debug_flags() & DBG_NO_GENO_REC) ? nullptr : st->geno_rec;
     D.go_stops = (const i64 *)st->geno_o_stops; D.ilens = st->ilens; D.v_starts = st->v_starts;
     D.n_variants = st->n_variants; D.keep = bt->keep; D.keep_offsets = (const i64 *)bt->keep_offsets;
     if (bt->batch > 0 && (!D.geno_offset_idx || !D.go_starts || !D.go_stops))
@@ -646,8 +621,25 @@ int gvl_pack_slots(const gvl_static *st, gvl_srec *srec_out, void *stream) {
     return check_launch("gvl_pack_slots");
 }
 
+// The static half of a batch's ReconArgs (memset first): the reference and -- unless ref_only -- the variant tables, with the records
+// GVL_DBG takes away left out
+static void static_args(ReconArgs &A, const gvl_static *st, int dbg, bool ref_only) {
+    memset(&A, 0, sizeof(A));
+    A.ref = st->ref; A.ref_len = st->ref_len; A.ref_offsets = (const i64 *)st->ref_offsets; A.pad = st->pad_char;
+    A.n_contigs = (int)(st->n_contigs < 0 ? 0 : (st->n_contigs > 0x7FFFFFFFll ? 0x7FFFFFFF : st->n_contigs));
+    if (ref_only) return;       // (get_reference: dbg stays 0 unless a lean route takes the rows)
+    A.dbg = dbg;
+    A.vrec = st->vrec; A.alt_offsets = (const i64 *)st->alt_offsets; A.alt_alleles = st->alt_alleles;
+    A.alt_len = st->alt_len; A.n_variants = st->n_variants;
+    A.go_starts = (const i64 *)st->geno_o_starts; A.go_stops = (const i64 *)st->geno_o_stops;
+    A.geno_v_idxs = st->geno_v_idxs;
+    A.grec = (dbg & DBG_NO_GENO_REC) ? nullptr : st->geno_rec;
+    A.srec = (dbg & (DBG_NO_SLOT_REC | DBG_NO_PACKABLE | DBG_SCALAR_WALK)) ? nullptr : st->slot_rec;
+    A.ref4 = st->ref4; A.slot_vidx = st->slot_vidx; A.n_geno_offsets = st->n_geno_offsets;
+}
+
 // validate one batch and fill its kernel arguments; `variant` = which template instance it needs
-static int fill_recon_args(const gvl_static *st, const gvl_batch *bt, const gvl_out *out, ReconArgs &A, int *chunks,
+static int fill_recon_args(const gvl_static *st, const gvl_batch *bt, const gvl_out *out, int dbg, ReconArgs &A, int *chunks,
                            int *variant) {
     if (!st || !bt || !out) return fail(GVL_ERR_INVALID, "%s", "gvl_reconstruct: NULL struct");
     if (bt->batch < 0 || bt->ploidy <= 0) return fail(GVL_ERR_INVALID, "%s", "gvl_reconstruct: bad batch/ploidy");
@@ -670,20 +662,9 @@ static int fill_recon_args(const gvl_static *st, const gvl_batch *bt, const gvl_
         return fail(GVL_ERR_INVALID, "%s", "gvl_reconstruct: bad onehot_layout");
     if (bt->batch * bt->ploidy > 0x7FFFFFFFll) return fail(GVL_ERR_INVALID, "%s", "gvl_reconstruct: batch too large for one launch");
 
-    memset(&A, 0, sizeof(A));
-    A.ref = st->ref; A.ref_len = st->ref_len; A.ref_offsets = (const i64 *)st->ref_offsets;
-    A.vrec = st->vrec; A.alt_offsets = (const i64 *)st->alt_offsets; A.alt_alleles = st->alt_alleles;
-    A.alt_len = st->alt_len; A.n_variants = st->n_variants;
-    A.go_starts = (const i64 *)st->geno_o_starts; A.go_stops = (const i64 *)st->geno_o_stops;
-    A.geno_v_idxs = st->geno_v_idxs;
-    A.grec = (debug_flags() & 16) ? nullptr : st->geno_rec;
-    A.srec = (debug_flags() & (64 | 512 | 8)) ? nullptr : st->slot_rec;
-    A.ref4 = st->ref4;
+    static_args(A, st, dbg, false);
     A.hplan = (const u32 *)bt->hap_plan;
     A.oh_cl = (out->onehot && out->onehot_layout == GVL_ONEHOT_CL) ? 1u : 0u;
-    A.slot_vidx = st->slot_vidx;
-    A.n_geno_offsets = st->n_geno_offsets;
-    A.n_contigs = (int)(st->n_contigs < 0 ? 0 : (st->n_contigs > 0x7FFFFFFFll ? 0x7FFFFFFF : st->n_contigs));
     A.regions = bt->regions; A.regions_stride = bt->regions_stride; A.shifts = bt->shifts;
     A.geno_offset_idx = (const i64 *)bt->geno_offset_idx;
     A.keep = bt->keep; A.keep_offsets = (const i64 *)bt->keep_offsets; A.to_rc = bt->to_rc;
@@ -701,9 +682,6 @@ static int fill_recon_args(const gvl_static *st, const gvl_batch *bt, const gvl_
     if (ml < 0) ml = 0;
     if (pick_chunk(ml, chunks, &A.chunk_len)) return fail(GVL_ERR_INVALID, "%s", "gvl_reconstruct: too many chunks");
     A.row_chunks = *chunks;
-    A.ref_only = 0;
-    A.dbg = debug_flags();
-    A.pad = st->pad_char;
     A.haps = out->haps; A.onehot = out->onehot;
     A.av = out->annot_v_idxs; A.ap = out->annot_ref_pos; A.out_offsets_w = bt->out_bounds ? nullptr : (i64 *)out->out_offsets;
     A.stamps = g_stamps;
@@ -714,73 +692,89 @@ static int fill_recon_args(const gvl_static *st, const gvl_batch *bt, const gvl_
     return GVL_OK;
 }
 
+// ---- routing: which of the three reconstruct kernels serves a batch ------------------------------------------------------
+//   reconstruct_kernel       the all-purpose kernel (gvl_recon.hip): every input, and every path GVL_DBG can force
+//   recon_lean_kernel        a wave per row, or per 2048-base chunk of longer rows (gvl_lean.hip)
+//   recon_lean_rows_kernel   the pipelined kernel: rows of one chunk, a group of batches in one grid (gvl_lean_pipe.hip)
+// Each C-ABI entry point reads GVL_DBG once (debug_flags) and routes on that one value, ReconArgs::dbg.
+//
+// The GVL_DBG bits each lean route tolerates -- whitelists: any other bit sends the batch to the all-purpose kernel.  Some bits
+// block a route only because they are missing from its list, not because they concern it; those are named next to the list.
+// DBG_OK_LEAN: fixed-length rows on the pipelined or the wave-per-row kernel (lean_eligible), ragged long rows on the chunked
+// kernel (lean_long_rag_eligible).  Incidental blockers: DBG_ABL_NO_VARIANTS, DBG_NO_FRONT, DBG_NO_BUCKET_INDEX, DBG_PAINT_TIMELINE,
+// DBG_PAINT_LDS_IMAGE (painter switches), DBG_DIFFS_WAVE_ROWS, DBG_TRACK_SIZING_PER_BATCH, DBG_RAGGED_PER_BATCH (loader switches).
+constexpr int DBG_OK_LEAN = DBG_ABL_NO_STORES | DBG_ABL_NO_LOADS | DBG_LEAN_SOLO | DBG_NO_REALIGN_LDS | DBG_ABL_NO_REALIGN |
+                            DBG_ABL_NO_ALLELES | DBG_NO_LEAN_LONG | DBG_PIPE_ALWAYS | DBG_PIPE_NEVER | DBG_NO_HAP_PLANS |
+                            DBG_ROUND4_ROUTES | DBG_NO_REALIGN_WINDOW | DBG_NO_FUSED_TRACKS | DBG_ABL_TRACK_WALK |
+                            DBG_ABL_TRACK_WINDOW | DBG_NO_TRACK_PLANS;
+// DBG_OK_PIPE_RAG: ragged rows on the pipelined kernel (lean_rag_eligible).  The same incidental blockers as DBG_OK_LEAN but
+// DBG_NO_FRONT, which this route reads.
+constexpr int DBG_OK_PIPE_RAG = (DBG_OK_LEAN | DBG_NO_FRONT) & ~DBG_PIPE_NEVER;
+// DBG_OK_REF_PIPE / DBG_OK_REF_CHUNKED: get_reference's rows (ref_only: no variants) on the pipelined / the chunked kernel
+// (ref_route).  Blocked on purpose by DBG_ROUND4_ROUTES, DBG_NO_LEAN and (pipelined) DBG_PIPE_NEVER / (chunked) DBG_NO_LEAN_LONG;
+// every other bit missing from the lists blocks them incidentally, e.g. DBG_SCALAR_WALK, DBG_NO_GENO_REC, DBG_NO_SLOT_REC,
+// DBG_NO_FRONT, the painter and loader switches and, on the pipelined route, DBG_ABL_NO_REALIGN.
+constexpr int DBG_OK_REF_PIPE = DBG_ABL_NO_STORES | DBG_ABL_NO_LOADS | DBG_LEAN_SOLO | DBG_NO_REALIGN_LDS | DBG_PIPE_ALWAYS |
+                                DBG_NO_TRACK_PLANS | DBG_NO_HAP_PLANS;
+constexpr int DBG_OK_REF_CHUNKED = DBG_OK_REF_PIPE | DBG_ABL_NO_REALIGN | DBG_PIPE_NEVER;
+
 // Can this batch take the lean kernel?  Row-major one-hot and / or haplotype bytes, fixed-length rows, no keep mask, no
 // annotations, the derived layouts present -- and no path-forcing debug flag (those exist to walk the all-purpose
 // kernel).  Rows of one chunk: one wave per row, variants from the slot lines.  Longer rows (a multiple of 4 bases, cut
 // into 2048-base chunks): one wave per chunk, variants from the CSR's inline records (LONG).
-static bool lean_eligible(const gvl_static *st, const gvl_batch *bt, const gvl_out *out, int chunks, int chunk_len) {
-    if (!st->ref4 || (!out->onehot && !out->haps)) return false;
+static bool lean_eligible(const gvl_static *st, const gvl_batch *bt, const gvl_out *out, int chunks, int chunk_len, int dbg) {
     // (annotated haplotypes: bytes + BOTH annotation streams (+ a one-hot in either layout), rows of one chunk, the slot records' variant indices present;
     // only the pipelined kernel has the form)
     // ... rows of several chunks (round 6): the chunked kernel's form, variant indices from the CSR's inline records
     if (out->annot_v_idxs || out->annot_ref_pos) {
-        if (!out->annot_v_idxs || !out->annot_ref_pos || !out->haps || (debug_flags() & 1073741824)) return false;
-        if (chunks == 1 && (!st->slot_vidx || ((uintptr_t)st->slot_vidx & 15) || (debug_flags() & 67108864))) return false;
+        if (!out->annot_v_idxs || !out->annot_ref_pos || !out->haps || (dbg & DBG_ROUND4_ROUTES)) return false;
+        if (chunks == 1 && (!st->slot_vidx || ((uintptr_t)st->slot_vidx & 15) || (dbg & DBG_PIPE_NEVER))) return false;
     }
     // (channel-major one-hot: the pipelined kernel's form for rows of one chunk, the chunked kernel's for long rows)
-    if (out->onehot && out->onehot_layout != GVL_ONEHOT_LC && ((chunks == 1 && (debug_flags() & 67108864)) || (debug_flags() & 1073741824))) return false;
+    if (out->onehot && out->onehot_layout != GVL_ONEHOT_LC && ((chunks == 1 && (dbg & DBG_PIPE_NEVER)) || (dbg & DBG_ROUND4_ROUTES))) return false;
     if (bt->out_offsets) return false;
-    // (a keep mask: both arrays or neither; rows of one chunk only, and only the pipelined kernel reads one)
-    if ((bt->keep != nullptr) != (bt->keep_offsets != nullptr)) return false;
     // (rows of one chunk: the pipelined kernel reads the mask; longer rows: the chunked kernel's walk and the chunk plans do, round 6)
-    if (bt->keep && ((chunks == 1 && (debug_flags() & 67108864)) || (debug_flags() & 1073741824))) return false;
+    if (bt->keep && ((chunks == 1 && (dbg & DBG_PIPE_NEVER)) || (dbg & DBG_ROUND4_ROUTES))) return false;
     if (bt->output_length <= 0 || (bt->output_length & 3)) return false;
     const i64 n_rows = bt->batch * bt->ploidy;
     if (chunks == 1) {
         if (!st->slot_rec || bt->output_length > LEAN_MAX_TRIPS * TRIP) return false;
-        if (n_rows <= 0 || n_rows > 0x7FFFFFF0ll) return false;     // (row indices are ints in the kernel)
+        if (n_rows > 0x7FFFFFF0ll) return false;     // (row indices are ints in the kernel)
     } else {
-        if (!st->geno_rec || chunk_len != LEAN_MAX_TRIPS * TRIP || (debug_flags() & 1048576)) return false;
-        if (n_rows <= 0 || n_rows * chunks > 0x7FFFFFF0ll) return false;                  // (wave indices are ints in the kernel)
+        if (!st->geno_rec || chunk_len != LEAN_MAX_TRIPS * TRIP || (dbg & DBG_NO_LEAN_LONG)) return false;
+        if (n_rows * chunks > 0x7FFFFFF0ll) return false;                  // (wave indices are ints in the kernel)
     }
-    if (st->alt_len >= (1ll << 32) || st->ref_len >= (1ll << 32) - 8192) return false;     // u32 positions in the kernel
-    // (2097152 ... 16777216 concern the track kernels only)
-    return (debug_flags() & ~(2 | 4 | 32768 | 65536 | 262144 | 524288 | 1048576 | 2097152 | 4194304 | 8388608 | 16777216 | 33554432 | 67108864 | 268435456 | 536870912 | 1073741824)) == 0;
+    return (dbg & ~DBG_OK_LEAN) == 0;
 }
 
 // ragged rows (out_offsets) longer than the pipelined form's 2560 bases: the chunked lean kernel's ragged form (<.., LONG, RAGL>)
-static bool lean_long_rag_eligible(const gvl_static *st, const gvl_batch *bt, const gvl_out *out, int chunks, int chunk_len) {
-    if (!st->ref4 || !st->geno_rec || (!out->onehot && !out->haps) || !bt->out_offsets) return false;
+static bool lean_long_rag_eligible(const gvl_static *st, const gvl_batch *bt, const gvl_out *out, int chunks, int chunk_len, int dbg) {
+    if (!st->geno_rec || !bt->out_offsets) return false;
     if (out->annot_v_idxs || out->annot_ref_pos || (out->onehot && out->onehot_layout != GVL_ONEHOT_LC)) return false;
-    if ((bt->keep != nullptr) != (bt->keep_offsets != nullptr)) return false;
-    if (bt->keep && (debug_flags() & 1073741824)) return false;           // (round 5's routing: rows under a keep mask on the all-purpose kernel)
-    if (chunks < 2 || chunk_len != LEAN_MAX_TRIPS * TRIP || (debug_flags() & (1048576 | 16))) return false;
-    const i64 n_rows = bt->batch * bt->ploidy;
-    if (n_rows <= 0 || n_rows * chunks > 0x7FFFFFF0ll) return false;
-    if (st->alt_len >= (1ll << 32) || st->ref_len >= (1ll << 32) - 8192) return false;
-    return (debug_flags() & ~(2 | 4 | 32768 | 65536 | 262144 | 524288 | 1048576 | 2097152 | 4194304 | 8388608 | 16777216 | 33554432 | 67108864 | 268435456 | 536870912 | 1073741824)) == 0;
+    if (bt->keep && (dbg & DBG_ROUND4_ROUTES)) return false;           // (round 5's routing: rows under a keep mask on the all-purpose kernel)
+    if (chunks < 2 || chunk_len != LEAN_MAX_TRIPS * TRIP || (dbg & (DBG_NO_LEAN_LONG | DBG_NO_GENO_REC))) return false;
+    if (bt->batch * bt->ploidy * chunks > 0x7FFFFFF0ll) return false;
+    return (dbg & ~DBG_OK_LEAN) == 0;
 }
 
 // ---- the pipelined form (gvl_lean_pipe.inc): rows of one chunk, `n` batches of the same shape in ONE grid ----------
 // Launches with fewer than 8192 rows keep recon_lean_kernel (a wave per row: with one row per wave there is nothing to
-// pipeline; gvl_set_tuning(GVL_TUNE_PIPE_MIN_ROWS) overrides); GVL_DBG & 33554432: always, with as few workgroups as 32 rows
-// per wave allow (the suite's small batches then run many rows per wave on ONE workgroup); GVL_DBG & 67108864: never.
+// pipeline; gvl_set_tuning(GVL_TUNE_PIPE_MIN_ROWS) overrides); DBG_PIPE_ALWAYS: always, with as few workgroups as 32 rows
+// per wave allow (the suite's small batches then run many rows per wave on ONE workgroup); DBG_PIPE_NEVER: never.
 // RAG: rows at out_offsets (ragged output, output_length = -1, or a caller's plan): row-major one-hot and / or bytes, no keep
 // mask, no annotations, the slot-major records and the packed reference present, and the caller's bound on the longest row
 // within the pipelined kernel's 10 trips.  There is no wave-per-row lean kernel for these: pipelined form or the all-purpose kernel.
-static bool lean_rag_eligible(const gvl_static *st, const gvl_batch *bt, const gvl_out *out) {
-    if (!st->ref4 || !st->slot_rec || (!out->onehot && !out->haps) || !bt->out_offsets) return false;
+static bool lean_rag_eligible(const gvl_static *st, const gvl_batch *bt, const gvl_out *out, int dbg, i64 mixed_t) {
+    if (!st->slot_rec || !bt->out_offsets) return false;
     if (out->onehot && out->onehot_layout != GVL_ONEHOT_LC) return false;
     if (out->annot_v_idxs || out->annot_ref_pos) {
         if (!out->annot_v_idxs || !out->annot_ref_pos || !out->haps || !st->slot_vidx || ((uintptr_t)st->slot_vidx & 15) ||
-            (debug_flags() & 1073741824)) return false;
+            (dbg & DBG_ROUND4_ROUTES)) return false;
     }
-    if ((bt->keep != nullptr) != (bt->keep_offsets != nullptr)) return false;
-    if (bt->keep && (debug_flags() & 1073741824)) return false;
+    if (bt->keep && (dbg & DBG_ROUND4_ROUTES)) return false;
     const i64 ml = bt->max_row_len > bt->output_length ? bt->max_row_len : bt->output_length;
     const i64 n_rows = bt->batch * bt->ploidy;
-    if (n_rows <= 0 || n_rows > 0x7FFFFFF0ll) return false;
-    if (ml <= 0) return false;
+    if (n_rows > 0x7FFFFFF0ll || ml <= 0) return false;
     if (ml > (i64)PIPE_RAG_MAXT * TRIP) {
         // a batch of MOSTLY short rows with a few long ones (a spliced batch: exons of a few hundred bases and the odd 3' UTR of several
         // thousand): the pipelined kernel still takes it -- a row beyond its 2560 bases is marked and written by its wave's solo path,
@@ -789,40 +783,86 @@ static bool lean_rag_eligible(const gvl_static *st, const gvl_batch *bt, const g
         // ... and the batch is large: a wave writes its long rows chunk by chunk at its end, which a launch of a few thousand rows has
         // nothing to hide behind (4 420 exon rows with 4 long ones: 27 us against the all-purpose kernel's 15; 17 372 rows: 34 against 40;
         // 69 586 rows: 89 against 152 -- tools/spliced_bench.py)
-        const i64 mixed_t = tune(GVL_TUNE_MIXED_MIN_ROWS);
         const i64 mixed_min = mixed_t > 0 ? mixed_t : 16384;
         if (bt->total_len_hint <= 0 || bt->total_len_hint / n_rows > (i64)PIPE_RAG_MAXT * TRIP / 2 || ml > 65536 || n_rows < mixed_min) return false;
     }
-    if (st->alt_len >= (1ll << 32) || st->ref_len >= (1ll << 32) - 8192) return false;
-    return (debug_flags() & ~(2 | 4 | 256 | 32768 | 65536 | 262144 | 524288 | 1048576 | 2097152 | 4194304 | 8388608 | 16777216 | 33554432 | 268435456 | 536870912 | 1073741824)) == 0;
+    return (dbg & ~DBG_OK_PIPE_RAG) == 0;
 }
-static bool lean_pipe_wanted(i64 total_rows, int n_batches = 1) {
-    if (debug_flags() & 67108864) return false;
-    if (debug_flags() & 33554432) return true;
-    const i64 min_t = tune(GVL_TUNE_PIPE_MIN_ROWS);
-    const i64 min_rows = min_t > 0 ? min_t : 8192;
-    // (a GROUP of small batches -- strong scaling: 4096 / 8 = 512 rows per rank and batch -- is one grid from 2048 rows on: ten
-    // launches of 512 rows are ten launch latencies in a row)
-    const i64 bar = (n_batches >= 2 && min_rows > 2048) ? 2048 : min_rows;
-    return total_rows >= bar;
+// What routing needs to know of one validated batch (fill_recon_args), computed once
+struct BatchFacts {
+    bool lean;          // lean_eligible: fixed-length rows the lean kernels take (one chunk: pipelined or wave per row; more: chunked)
+    bool rag;           // lean_rag_eligible: ragged rows the pipelined kernel takes
+    bool long_rag;      // lean_long_rag_eligible: ragged rows the chunked kernel takes
+    bool pipe_form;     // rows of one chunk in a form only the pipelined kernel has: channel-major one-hot, a keep mask, annotations
+};
+static BatchFacts batch_facts(const gvl_static *st, const gvl_batch *bt, const gvl_out *out, const ReconArgs &A, int chunks,
+                              i64 mixed_t) {
+    BatchFacts f{false, false, false, chunks == 1 && (A.oh_cl || A.keep || A.av)};
+    // what every lean route needs: rows (not at out_bounds pairs -- the all-purpose kernel's row setup reads those), the packed
+    // reference, a keep mask's two arrays or neither, u32 positions
+    if (A.n_rows <= 0 || bt->out_bounds || !st->ref4 || (bt->keep != nullptr) != (bt->keep_offsets != nullptr) ||
+        st->alt_len >= (1ll << 32) || st->ref_len >= (1ll << 32) - 8192) return f;
+    f.lean = lean_eligible(st, bt, out, chunks, A.chunk_len, A.dbg);
+    f.rag = lean_rag_eligible(st, bt, out, A.dbg, mixed_t);
+    f.long_rag = lean_long_rag_eligible(st, bt, out, chunks, A.chunk_len, A.dbg);
+    return f;
 }
-int gvl_reconstruct(const gvl_static *st, const gvl_batch *bt, const gvl_out *out, void *stream) {
-    ReconArgs A;
-    int chunks = 1, variant = 0;
-    const int rc = fill_recon_args(st, bt, out, A, &chunks, &variant);
-    if (rc) return rc;
-    if (bt->out_bounds) return launch_recon(A, chunks, variant, stream);      // (scatter write: the all-purpose kernel's row setup reads the pairs)
-    if (A.n_rows > 0 && lean_eligible(st, bt, out, chunks, A.chunk_len)) {
-        // (rows of one chunk: only the pipelined kernel has the channel-major and annotated forms and reads keep masks)
-        const bool pipe_only = chunks == 1 && (A.oh_cl || A.keep || A.av);
-        if (chunks == 1 && (lean_pipe_wanted(A.n_rows) || pipe_only) && lean_pipe_compatible(&A, 1)) return launch_lean_rows(&A, 1, stream, 1);
-        if (pipe_only) return launch_recon(A, chunks, variant, stream);
-        return launch_lean(A, chunks, stream);
+
+// Launches `n` validated batches (gvl_reconstruct: n = 1, many = false): ONE pipelined grid over all of them when they allow it,
+// else a launch per batch.  pipe_min_t: gvl_set_tuning(GVL_TUNE_PIPE_MIN_ROWS).
+static int route_reconstruct(const ReconArgs *A, const BatchFacts *f, const int *chunks, const int *variant, int n, bool many,
+                             i64 pipe_min_t, void *stream) {
+    bool all_one_chunk_lean = n > 0, all_rag = n > 0, any_form = false;
+    i64 total = 0;
+    int min_chunks = n > 0 ? chunks[0] : 1;     // (LeanArgs.max_row_len: the smallest bound; a row is reported against its own batch's, ReconArgs.row_chunks)
+    for (int i = 0; i < n; ++i) {
+        all_one_chunk_lean = all_one_chunk_lean && f[i].lean && chunks[i] == 1;
+        all_rag = all_rag && f[i].rag;
+        any_form = any_form || f[i].pipe_form;
+        total += A[i].n_rows;
+        min_chunks = chunks[i] < min_chunks ? chunks[i] : min_chunks;
     }
-    if (A.n_rows > 0 && !(debug_flags() & 67108864) && lean_rag_eligible(st, bt, out) && lean_pipe_compatible(&A, 1))
-        return launch_lean_rows(&A, 1, stream, chunks);
-    if (A.n_rows > 0 && lean_long_rag_eligible(st, bt, out, chunks, A.chunk_len)) return launch_lean(A, chunks, stream);
-    return launch_recon(A, chunks, variant, stream);
+    // Rows of one chunk: the pipelined kernel from 8192 rows on (a wave per row below: with one row per wave there is nothing to
+    // pipeline), or from 2048 for a GROUP of small batches (strong scaling: 4096 / 8 = 512 rows per rank and batch; ten launches of
+    // 512 rows are ten launch latencies in a row); always for the forms only it has.  DBG_PIPE_ALWAYS: always, with as few
+    // workgroups as 32 rows per wave allow (the suite's small batches then run many rows per wave on ONE workgroup); DBG_PIPE_NEVER: never.
+    const i64 min_rows = pipe_min_t > 0 ? pipe_min_t : 8192;
+    const bool pipe_wanted = !(A[0].dbg & DBG_PIPE_NEVER) &&
+                             ((A[0].dbg & DBG_PIPE_ALWAYS) || total >= ((n >= 2 && min_rows > 2048) ? 2048 : min_rows));
+    if (all_one_chunk_lean && (pipe_wanted || any_form) && lean_pipe_compatible(A, n)) return launch_lean_rows(A, n, stream, 1);
+    if (all_rag && lean_pipe_compatible(A, n)) return launch_lean_rows(A, n, stream, min_chunks);
+    for (int i = 0; i < n; ++i) {
+        // One batch alone: ragged rows the pipelined kernel could not take go to the chunked kernel if it can.  gvl_reconstruct_many's
+        // fallback routes a leftover batch differently from gvl_reconstruct: a batch eligible for the pipelined ragged route gets the
+        // all-purpose kernel, and one of a single chunk that would be pipelined alone (>= 8192 rows) gets the wave-per-row kernel.
+        const bool lean = f[i].lean || (f[i].long_rag && !(many && f[i].rag));
+        int rc;
+        if (f[i].lean && f[i].pipe_form)
+            rc = lean_pipe_compatible(&A[i], 1) ? launch_lean_rows(&A[i], 1, stream, 1) : launch_recon(A[i], chunks[i], variant[i], stream);
+        else
+            rc = lean ? launch_lean(A[i], chunks[i], stream) : launch_recon(A[i], chunks[i], variant[i], stream);
+        if (rc) return rc;
+    }
+    return GVL_OK;
+}
+
+// gvl_reconstruct (n = 1) and gvl_reconstruct_many: every batch validated before the first launch
+static int reconstruct_batches(const gvl_static *st, const gvl_batch *bts, const gvl_out *outs, int n, bool many, void *stream) {
+    const int dbg = debug_flags();
+    const i64 mixed_t = tune(GVL_TUNE_MIXED_MIN_ROWS);
+    ReconArgs A[GVL_MANY_MAX];
+    int chunks[GVL_MANY_MAX], variant[GVL_MANY_MAX];
+    BatchFacts f[GVL_MANY_MAX];
+    for (int i = 0; i < n; ++i) {
+        const int rc = fill_recon_args(st, &bts[i], &outs[i], dbg, A[i], &chunks[i], &variant[i]);
+        if (rc) return rc;
+        f[i] = batch_facts(st, &bts[i], &outs[i], A[i], chunks[i], mixed_t);
+    }
+    return route_reconstruct(A, f, chunks, variant, n, many, tune(GVL_TUNE_PIPE_MIN_ROWS), stream);
+}
+
+int gvl_reconstruct(const gvl_static *st, const gvl_batch *bt, const gvl_out *out, void *stream) {
+    return reconstruct_batches(st, bt, out, 1, false, stream);
 }
 
 // `n` batches in one host call.  Batches the lean kernel's pipelined form can take together (one-chunk rows, the same
@@ -833,37 +873,7 @@ int gvl_reconstruct(const gvl_static *st, const gvl_batch *bt, const gvl_out *ou
 // Everything else: back-to-back launches on `stream`, every batch validated before the first launch.
 int gvl_reconstruct_many(const gvl_static *st, const gvl_batch *bts, const gvl_out *outs, int32_t n, void *stream) {
     if (n < 0 || n > GVL_MANY_MAX || (n > 0 && (!bts || !outs))) return fail(GVL_ERR_INVALID, "%s", "gvl_reconstruct_many: bad arguments (n <= GVL_MANY_MAX)");
-    ReconArgs A[GVL_MANY_MAX];
-    int chunks[GVL_MANY_MAX], variant[GVL_MANY_MAX];
-    bool lean[GVL_MANY_MAX];
-    bool all_one_chunk_lean = n > 0, all_rag = n > 0 && !(debug_flags() & 67108864), any_cl = false;
-    i64 total = 0;
-    for (int i = 0; i < n; ++i) {
-        chunks[i] = 1; variant[i] = 0;
-        const int rc = fill_recon_args(st, &bts[i], &outs[i], A[i], &chunks[i], &variant[i]);
-        if (rc) return rc;
-        lean[i] = A[i].n_rows > 0 && !bts[i].out_bounds && (lean_eligible(st, &bts[i], &outs[i], chunks[i], A[i].chunk_len) ||
-                                      (!lean_rag_eligible(st, &bts[i], &outs[i]) && lean_long_rag_eligible(st, &bts[i], &outs[i], chunks[i], A[i].chunk_len)));
-        all_one_chunk_lean = all_one_chunk_lean && lean[i] && chunks[i] == 1;
-        any_cl = any_cl || (chunks[i] == 1 && (A[i].oh_cl || A[i].keep || A[i].av));
-        all_rag = all_rag && A[i].n_rows > 0 && !bts[i].out_bounds && lean_rag_eligible(st, &bts[i], &outs[i]);
-        total += A[i].n_rows;
-    }
-    if (all_one_chunk_lean && (lean_pipe_wanted(total, n) || any_cl) && lean_pipe_compatible(A, n)) return launch_lean_rows(A, n, stream, 1);
-    if (all_rag && lean_pipe_compatible(A, n)) {
-        int min_chunks = chunks[0];             // (LeanArgs.max_row_len: the smallest bound; a row is reported against its own batch's, ReconArgs.row_chunks)
-        for (int i = 1; i < n; ++i) min_chunks = chunks[i] < min_chunks ? chunks[i] : min_chunks;
-        return launch_lean_rows(A, n, stream, min_chunks);
-    }
-    for (int i = 0; i < n; ++i) {
-        int rc;
-        if (lean[i] && chunks[i] == 1 && (A[i].oh_cl || A[i].keep || A[i].av))       // (channel-major one-hot, a keep mask: the pipelined kernel's forms, or the all-purpose kernel)
-            rc = lean_pipe_compatible(&A[i], 1) ? launch_lean_rows(&A[i], 1, stream, 1) : launch_recon(A[i], chunks[i], variant[i], stream);
-        else
-            rc = lean[i] ? launch_lean(A[i], chunks[i], stream) : launch_recon(A[i], chunks[i], variant[i], stream);
-        if (rc) return rc;
-    }
-    return GVL_OK;
+    return reconstruct_batches(st, bts, outs, n, true, stream);
 }
 
 int64_t gvl_hap_plan_bytes(int64_t n_rows, int64_t output_length) {
@@ -883,113 +893,91 @@ int gvl_hap_plan(const gvl_static *st, const gvl_batch *bt, void *plan, void *st
         return fail(GVL_ERR_UNSUPPORTED, "%s", "gvl_hap_plan: rows of 2 .. 512 chunks of 2048 bases (a multiple of 4 bases) only");
     if (!st->ref_offsets || !st->geno_o_starts || !st->geno_o_stops || !bt->regions || !bt->shifts || !bt->geno_offset_idx || bt->regions_stride < 3)
         return fail(GVL_ERR_INVALID, "%s", "gvl_hap_plan: NULL/invalid array");
+    const int dbg = debug_flags();
     ReconArgs A;
-    memset(&A, 0, sizeof(A));
-    A.ref_offsets = (const i64 *)st->ref_offsets; A.alt_offsets = (const i64 *)st->alt_offsets;
-    A.go_starts = (const i64 *)st->geno_o_starts; A.go_stops = (const i64 *)st->geno_o_stops;
-    A.grec = (debug_flags() & 16) ? nullptr : st->geno_rec;       // (without the inline records no chunk is planned: every one flagged)
-    A.n_geno_offsets = st->n_geno_offsets;
-    A.n_contigs = (int)(st->n_contigs < 0 ? 0 : (st->n_contigs > 0x7FFFFFFFll ? 0x7FFFFFFF : st->n_contigs));
+    static_args(A, st, dbg, false);      // (without the inline records -- DBG_NO_GENO_REC -- no chunk is planned: every one flagged)
+    A.ref4 = nullptr; A.srec = nullptr; A.alt_alleles = nullptr;      // (the planner's arguments carry none of these)
     A.regions = bt->regions; A.regions_stride = bt->regions_stride; A.shifts = bt->shifts;
     A.geno_offset_idx = (const i64 *)bt->geno_offset_idx;
     A.keep = bt->keep; A.keep_offsets = (const i64 *)bt->keep_offsets;       // (a plan made under a keep mask is that mask's)
     A.fixed_len = bt->output_length;
     A.n_rows = bt->batch * bt->ploidy; A.ploidy = (int)bt->ploidy; A.ploidy_shift = log2_exact(bt->ploidy);
-    A.dbg = debug_flags();
     int chunks = 1;
     if (pick_chunk(bt->output_length, &chunks, &A.chunk_len)) return fail(GVL_ERR_INVALID, "%s", "gvl_hap_plan: too many chunks");
     return launch_hap_plan(A, chunks, (u32 *)plan, stream);
 }
 
+// ---- get_reference: rows = regions (the third column is the end), no variants, no shift (ReconArgs::ref_only) ----
+// validate one batch (n_rows > 0) and fill its arguments as the all-purpose kernel takes them (the lean routes add ref4, dbg, async_err)
+static int ref_args(const gvl_static *st, const gvl_ref_batch &b, const char *who, ReconArgs &A, int *chunks) {
+    if ((st->ref_len > 0 && !st->ref) || !st->ref_offsets || !b.regions || !b.out_offsets || b.regions_stride < 3 || (!b.out && !b.onehot))
+        return fail(GVL_ERR_INVALID, "%s: NULL/invalid array", who);
+    if (b.max_row_len < 0 || b.max_row_len > 0x7FFFFF00ll) return fail(GVL_ERR_INVALID, "%s: bad max_row_len", who);
+    if (b.n_rows > 0x7FFFFFFFll) return fail(GVL_ERR_INVALID, "%s: batch too large", who);
+    static_args(A, st, 0, true);
+    A.regions = b.regions; A.regions_stride = b.regions_stride;
+    A.to_rc = b.to_rc; A.out_offsets = (const i64 *)b.out_offsets; A.fixed_len = -1;
+    A.n_rows = b.n_rows; A.ploidy = 1; A.ploidy_shift = 0;
+    if (pick_chunk(b.max_row_len, chunks, &A.chunk_len)) return fail(GVL_ERR_INVALID, "%s", "gvl_get_reference: too many chunks");
+    A.row_chunks = *chunks;
+    A.ref_only = 1;
+    A.haps = b.out; A.onehot = b.onehot;
+    return GVL_OK;
+}
+// Rows of at most 2560 bases with the packed reference present: the pipelined lean kernel's ragged form with no slot lines (a row
+// inside its contig is one window read + the stream; rows that need padding run the all-purpose body at their wave's end).
+// Longer rows (`with_seqs("reference")` at Enformer length): the chunked lean kernel's ragged form, a wave per 2048-base chunk with
+// no walk at all.  Anything else, or a GVL_DBG bit outside the route's list: the all-purpose kernel.
+enum Kernel { K_RECON, K_LEAN, K_PIPE };      // reconstruct_kernel, recon_lean_kernel, recon_lean_rows_kernel
+static Kernel ref_route(const gvl_static *st, const ReconArgs &A, int chunks, i64 max_row_len, int dbg) {
+    if (!st->ref4 || st->ref_len >= (1ll << 32) - 8192) return K_RECON;
+    if (!((uintptr_t)st->ref4 & 15) && max_row_len > 0 && max_row_len <= (i64)PIPE_RAG_MAXT * TRIP && A.n_rows <= 0x7FFFFFF0ll &&
+        (dbg & ~DBG_OK_REF_PIPE) == 0) return K_PIPE;
+    if (chunks >= 2 && A.chunk_len == LEAN_MAX_TRIPS * TRIP && A.n_rows * (i64)chunks <= 0x7FFFFFF0ll && (dbg & ~DBG_OK_REF_CHUNKED) == 0)
+        return K_LEAN;
+    return K_RECON;
+}
+
+// gvl_get_reference (n = 1) and gvl_get_reference_many: every batch checked before anything is launched; ONE grid over the group
+// when every batch takes the pipelined route on its own and they share a shape, else each batch by its own route
+static int get_reference_batches(const gvl_static *st, const gvl_ref_batch *bs, int n, const char *who, void *stream) {
+    const int dbg = debug_flags();
+    ReconArgs A[GVL_MANY_MAX];
+    int chunks[GVL_MANY_MAX];
+    Kernel k[GVL_MANY_MAX];
+    bool grouped = n >= 2;
+    int min_chunks = 0x7FFFFFFF;
+    for (int i = 0; i < n; ++i) {
+        if (bs[i].n_rows < 0) return fail(GVL_ERR_INVALID, "%s: bad arguments", who);
+        if (bs[i].n_rows == 0) { grouped = false; continue; }
+        const int rc = ref_args(st, bs[i], who, A[i], &chunks[i]);
+        if (rc) return rc;
+        k[i] = ref_route(st, A[i], chunks[i], bs[i].max_row_len, dbg);
+        if (k[i] != K_RECON) { A[i].ref4 = st->ref4; A[i].dbg = dbg; A[i].async_err = async_err_word(); }
+        grouped = grouped && k[i] == K_PIPE;
+        min_chunks = chunks[i] < min_chunks ? chunks[i] : min_chunks;
+    }
+    if (grouped && lean_pipe_compatible(A, n)) return launch_lean_rows(A, n, stream, min_chunks);
+    for (int i = 0; i < n; ++i) {
+        if (bs[i].n_rows == 0) continue;
+        const int rc = k[i] == K_PIPE ? launch_lean_rows(&A[i], 1, stream, chunks[i]) : k[i] == K_LEAN ? launch_lean(A[i], chunks[i], stream)
+                     : launch_recon(A[i], chunks[i], (bs[i].onehot ? OH_LC : OH_NONE) | (bs[i].out ? 4 : 0), stream);    // (A.dbg stays 0 here)
+        if (rc) return rc;
+    }
+    return GVL_OK;
+}
+
 int gvl_get_reference(const gvl_static *st, const int32_t *regions, int64_t regions_stride,
                       int64_t n_rows, const int64_t *out_offsets, int64_t max_row_len,
                       const uint8_t *to_rc, uint8_t *out, uint8_t *onehot, void *stream) {
-    if (!st || n_rows < 0) return fail(GVL_ERR_INVALID, "%s", "gvl_get_reference: bad arguments");
-    if (n_rows == 0) return GVL_OK;
-    if ((st->ref_len > 0 && !st->ref) || !st->ref_offsets || !regions || !out_offsets || regions_stride < 3 || (!out && !onehot))
-        return fail(GVL_ERR_INVALID, "%s", "gvl_get_reference: NULL/invalid array");
-    if (max_row_len < 0 || max_row_len > 0x7FFFFF00ll)
-        return fail(GVL_ERR_INVALID, "%s", "gvl_get_reference: bad max_row_len");
-    ReconArgs A;
-    memset(&A, 0, sizeof(A));
-    A.ref = st->ref; A.ref_len = st->ref_len; A.ref_offsets = (const i64 *)st->ref_offsets;
-    A.regions = regions; A.regions_stride = regions_stride;
-    A.n_contigs = (int)(st->n_contigs < 0 ? 0 : (st->n_contigs > 0x7FFFFFFFll ? 0x7FFFFFFF : st->n_contigs));
-    A.to_rc = to_rc; A.out_offsets = (const i64 *)out_offsets; A.fixed_len = -1;
-    A.n_rows = n_rows; A.ploidy = 1; A.ploidy_shift = 0;
-    int chunks = 1;
-    if (pick_chunk(max_row_len, &chunks, &A.chunk_len)) return fail(GVL_ERR_INVALID, "%s", "gvl_get_reference: too many chunks");
-    A.row_chunks = chunks;
-    A.ref_only = 1;
-    A.pad = st->pad_char;
-    A.haps = out; A.onehot = onehot;
-    if (n_rows > 0x7FFFFFFFll) return fail(GVL_ERR_INVALID, "%s", "gvl_get_reference: batch too large");
-    // Rows of at most 2560 bases with the packed reference present: the pipelined lean kernel's ragged form with no slot lines (a row
-    // inside its contig is one window read + the stream; rows that need padding run the all-purpose body at their wave's end).
-    // GVL_DBG 2^30 / 67108864: the all-purpose kernel for every row, as until round 4.
-    if (st->ref4 && !((uintptr_t)st->ref4 & 15) && max_row_len > 0 && max_row_len <= (i64)PIPE_RAG_MAXT * TRIP && n_rows <= 0x7FFFFFF0ll &&
-        st->ref_len < (1ll << 32) - 8192 &&
-        (debug_flags() & ~(2 | 4 | 32768 | 65536 | 33554432 | 268435456 | 536870912)) == 0) {
-        A.ref4 = st->ref4;
-        A.dbg = debug_flags();
-        A.async_err = async_err_word();
-        return launch_lean_rows(&A, 1, stream, chunks);
-    }
-    // Longer rows (`with_seqs("reference")` at Enformer length): the chunked lean kernel's ragged form, a wave per 2048-base chunk with
-    // no walk at all.  GVL_DBG 2^30 / 1048576: the all-purpose kernel.
-    if (st->ref4 && chunks >= 2 && A.chunk_len == LEAN_MAX_TRIPS * TRIP && n_rows * (i64)chunks <= 0x7FFFFFF0ll &&
-        st->ref_len < (1ll << 32) - 8192 && (debug_flags() & ~(2 | 4 | 32768 | 65536 | 262144 | 33554432 | 67108864 | 268435456 | 536870912)) == 0) {
-        A.ref4 = st->ref4;
-        A.dbg = debug_flags();
-        A.async_err = async_err_word();
-        return launch_lean(A, chunks, stream);
-    }
-    return launch_recon(A, chunks, (onehot ? OH_LC : OH_NONE) | (out ? 4 : 0), stream);
+    if (!st) return fail(GVL_ERR_INVALID, "%s", "gvl_get_reference: bad arguments");
+    const gvl_ref_batch b{regions, regions_stride, n_rows, out_offsets, max_row_len, to_rc, out, onehot};
+    return get_reference_batches(st, &b, 1, "gvl_get_reference", stream);
 }
 
 int gvl_get_reference_many(const gvl_static *st, const gvl_ref_batch *bs, int32_t n, void *stream) {
     if (!st || n < 0 || n > GVL_MANY_MAX || (n > 0 && !bs)) return fail(GVL_ERR_INVALID, "%s", "gvl_get_reference_many: bad arguments (n <= GVL_MANY_MAX)");
-    // one grid over the group when every batch could take the pipelined route on its own and they share a shape
-    ReconArgs A[GVL_MANY_MAX];
-    bool grouped = n >= 2 && st->ref4 && !((uintptr_t)st->ref4 & 15) && st->ref_offsets && st->ref_len < (1ll << 32) - 8192 &&
-                   (debug_flags() & ~(2 | 4 | 32768 | 65536 | 33554432 | 268435456 | 536870912)) == 0;
-    int min_chunks = 0x7FFFFFFF;
-    // every batch is validated before anything is launched (as gvl_reconstruct_many does), with gvl_get_reference's own checks
-    for (int i = 0; i < n; ++i) {
-        const gvl_ref_batch &b = bs[i];
-        if (b.n_rows < 0) return fail(GVL_ERR_INVALID, "%s", "gvl_get_reference_many: bad arguments");
-        if (b.n_rows == 0) continue;
-        if ((st->ref_len > 0 && !st->ref) || !st->ref_offsets || !b.regions || !b.out_offsets || b.regions_stride < 3 || (!b.out && !b.onehot))
-            return fail(GVL_ERR_INVALID, "%s", "gvl_get_reference_many: NULL/invalid array");
-        if (b.max_row_len < 0 || b.max_row_len > 0x7FFFFF00ll) return fail(GVL_ERR_INVALID, "%s", "gvl_get_reference_many: bad max_row_len");
-        if (b.n_rows > 0x7FFFFFFFll) return fail(GVL_ERR_INVALID, "%s", "gvl_get_reference_many: batch too large");
-    }
-    grouped = grouped && (st->ref_len == 0 || st->ref);
-    for (int i = 0; i < n && grouped; ++i) {
-        const gvl_ref_batch &b = bs[i];
-        if (b.n_rows <= 0 || b.n_rows > 0x7FFFFFF0ll || !b.regions || !b.out_offsets || b.regions_stride < 3 || (!b.out && !b.onehot) ||
-            b.max_row_len <= 0 || b.max_row_len > (i64)PIPE_RAG_MAXT * TRIP) { grouped = false; break; }
-        ReconArgs &R = A[i];
-        memset(&R, 0, sizeof(R));
-        R.ref = st->ref; R.ref_len = st->ref_len; R.ref_offsets = (const i64 *)st->ref_offsets; R.ref4 = st->ref4;
-        R.regions = b.regions; R.regions_stride = b.regions_stride;
-        R.n_contigs = (int)(st->n_contigs < 0 ? 0 : (st->n_contigs > 0x7FFFFFFFll ? 0x7FFFFFFF : st->n_contigs));
-        R.to_rc = b.to_rc; R.out_offsets = (const i64 *)b.out_offsets; R.fixed_len = -1;
-        R.n_rows = b.n_rows; R.ploidy = 1; R.ploidy_shift = 0;
-        int chunks = 1;
-        if (pick_chunk(b.max_row_len, &chunks, &R.chunk_len)) { grouped = false; break; }
-        R.row_chunks = chunks;
-        min_chunks = chunks < min_chunks ? chunks : min_chunks;
-        R.ref_only = 1; R.pad = st->pad_char; R.haps = b.out; R.onehot = b.onehot;
-        R.dbg = debug_flags(); R.async_err = async_err_word();
-    }
-    if (grouped && lean_pipe_compatible(A, n)) return launch_lean_rows(A, n, stream, min_chunks);
-    for (int i = 0; i < n; ++i) {
-        const int rc = gvl_get_reference(st, bs[i].regions, bs[i].regions_stride, bs[i].n_rows, bs[i].out_offsets, bs[i].max_row_len, bs[i].to_rc,
-                                         bs[i].out, bs[i].onehot, stream);
-        if (rc) return rc;
-    }
-    return GVL_OK;
+    return get_reference_batches(st, bs, n, "gvl_get_reference_many", stream);
 }
 
 int gvl_get_diffs_sparse(const gvl_static *st, const gvl_batch *bt, const int32_t *q_starts,
@@ -1001,7 +989,7 @@ int gvl_get_diffs_sparse(const gvl_static *st, const gvl_batch *bt, const int32_
     if (!diffs) return fail(GVL_ERR_INVALID, "%s", "gvl_get_diffs_sparse: NULL diffs");
     D.q_starts = q_starts; D.q_ends = q_ends; D.q_stride = q_stride > 0 ? q_stride : 1;
     D.diffs = diffs; D.output_length = 0; D.lengths = nullptr;
-    if (diffs_long_rows(st)) {
+    if (diffs_long_rows(st, debug_flags())) {
         const i64 grid = (D.n_rows * WAVE + 255) / 256;
         if (grid > 0x7FFFFFFFll) return fail(GVL_ERR_INVALID, "%s", "gvl_get_diffs_sparse: batch too large");
         hipLaunchKernelGGL(diffs_wave_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, D, (const int *)nullptr, (i64)0);
@@ -1035,7 +1023,7 @@ static int hap_offsets_impl(const gvl_static *st, const gvl_batch *bt, int32_t *
     D.q_starts = bt->regions + 1; D.q_ends = bt->regions + 2; D.q_stride = bt->regions_stride;
     D.diffs = diffs; D.output_length = bt->output_length; D.lengths = (i64 *)out_offsets;
     if (len_cap > 0) { D.len_cap = len_cap; D.async_err = async_err_word(); }
-    if (diffs_long_rows(st)) {
+    if (diffs_long_rows(st, debug_flags())) {
         const i64 grid = (D.n_rows * WAVE + 255) / 256;
         if (grid > 0x7FFFFFFFll) return fail(GVL_ERR_INVALID, "%s", "gvl_hap_offsets: batch too large");
         hipLaunchKernelGGL(diffs_wave_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, D, bt->regions, (i64)bt->regions_stride);
@@ -1141,7 +1129,7 @@ int gvl_prepare_request(const gvl_static *st, const int64_t *idx, int64_t batch,
         if (!st || !st->geno_o_starts || !st->geno_o_stops || (st->n_geno > 0 && (!st->geno_v_idxs || !st->ilens || !st->v_starts)))
             return fail(GVL_ERR_INVALID, "%s", "gvl_prepare_request: random shifts need the genotype CSR + variant table");
         P.D.geno_v_idxs = st->geno_v_idxs; P.D.go_starts = (const i64 *)st->geno_o_starts;
-        P.D.grec = (debug_flags() & 16) ? nullptr : st->geno_rec;
+        P.D.grec = (debug_flags() & DBG_NO_GENO_REC) ? nullptr : st->geno_rec;
         P.D.go_stops = (const i64 *)st->geno_o_stops; P.D.ilens = st->ilens; P.D.v_starts = st->v_starts;
         P.D.n_variants = st->n_variants; P.D.n_rows = batch * ploidy;
     }
@@ -1192,10 +1180,11 @@ __global__ __launch_bounds__(256) void batch_seeds_kernel(const i64 *order, i64 
 // the table: gvl_loader_start_epoch, the fill and every submit of the epoch take them from that one snapshot, and a table that was
 // prefetched under other knobs is simply filled again.  (They were re-read at three different times: a gvl_set_tuning /
 // gvl_set_debug_flags between a prefetch and the epoch's start made the part offsets disagree.)
+constexpr int DBG_LOADER_KNOBS = DBG_SCALAR_WALK | DBG_DIFFS_WAVE_ROWS | DBG_RAGGED_PER_BATCH | DBG_NO_TRACK_PLANS | DBG_NO_HAP_PLANS;
 struct LoaderKnobs {
     i64 track_cap_mb, hap_cap_mb;   // GVL_TUNE_TRACK_PLAN_MAX_MB / GVL_TUNE_HAP_PLAN_MAX_MB (0: built in)
     int ragged_per_group;           // GVL_TUNE_RAGGED_SIZING == 1
-    int dbg;                        // the GVL_DBG bits that decide what a table holds: 8, 2048, 134217728, 268435456, 536870912
+    int dbg;                        // the GVL_DBG bits that decide what a table holds (DBG_LOADER_KNOBS)
     bool operator==(const LoaderKnobs &o) const {
         return track_cap_mb == o.track_cap_mb && hap_cap_mb == o.hap_cap_mb && ragged_per_group == o.ragged_per_group && dbg == o.dbg;
     }
@@ -1253,7 +1242,7 @@ static LoaderKnobs loader_knobs_now() {
     LoaderKnobs k;
     k.track_cap_mb = tune(GVL_TUNE_TRACK_PLAN_MAX_MB); k.hap_cap_mb = tune(GVL_TUNE_HAP_PLAN_MAX_MB);
     k.ragged_per_group = tune(GVL_TUNE_RAGGED_SIZING) == 1 ? 1 : 0;
-    k.dbg = debug_flags() & (8 | 2048 | 134217728 | 268435456 | 536870912);
+    k.dbg = debug_flags() & DBG_LOADER_KNOBS;
     return k;
 }
 static i64 loader_track_plan_bytes(const gvl_loader_config *cfg, i64 n, const LoaderKnobs &kn) {
@@ -1281,12 +1270,9 @@ static i64 loader_hap_plan_bytes(const gvl_loader_config *cfg, i64 n, const Load
 
 static bool loader_ragged(const gvl_loader_config *c) { return c->output_length == -1; }
 // ragged rows are sized once per EPOCH (in the table) instead of once per group of batches -- whenever the group sizing would be
-// used; gvl_set_tuning(GVL_TUNE_RAGGED_SIZING, 1): per group, as in round 4 (GVL_DBG & 134217728: per batch, as before that)
-static bool loader_long_rows(const gvl_static *st, const LoaderKnobs &kn) {      // (diffs_long_rows under the snapshot's GVL_DBG 2048)
-    return (kn.dbg & 2048) || (st->n_geno_offsets > 0 && st->n_geno / st->n_geno_offsets > 16);
-}
+// used; gvl_set_tuning(GVL_TUNE_RAGGED_SIZING, 1): per group, as in round 4 (DBG_RAGGED_PER_BATCH: per batch, as before that)
 static bool loader_epoch_sizing(const gvl_static *st, const gvl_loader_config *c, const LoaderKnobs &kn) {
-    return loader_ragged(c) && !loader_long_rows(st, kn) && !(kn.dbg & 134217728) && !kn.ragged_per_group;
+    return loader_ragged(c) && !diffs_long_rows(st, kn.dbg) && !(kn.dbg & DBG_RAGGED_PER_BATCH) && !kn.ragged_per_group;
 }
 // bases per row a slot reserves: the fixed length, or the ragged bound
 static i64 loader_row_cap(const gvl_loader_config *c) { return loader_ragged(c) ? c->max_row_len : c->output_length; }
@@ -1444,7 +1430,7 @@ static int loader_fill_table(gvl_loader *ld, const int64_t *order, i64 n, int32_
                                        c.rc_neg, c.deterministic, c.output_length < 0 ? 0 : c.output_length, c.seed, counter,
                                        t_regions, (int64_t *)t_goi, t_to_rc, t_shifts, s);
     if (rc) return rc;
-    if (po[9] > po[8] && !(kn.dbg & 536870912)) {
+    if (po[9] > po[8] && !(kn.dbg & DBG_NO_HAP_PLANS)) {
         // rows of several chunks: every row's chunk plans, once per epoch (the batches' launches get pointers into them)
         gvl_batch gb;
         memset(&gb, 0, sizeof(gb));
@@ -1503,12 +1489,12 @@ static int loader_fill_table(gvl_loader *ld, const int64_t *order, i64 n, int32_
         rc3 = check_launch("gvl_loader_start_epoch(track offsets)");
         if (rc3) return rc3;
         // rows of several chunks: the rows' plans (track_plan_kernel), for every row of the epoch
-        if (po[8] > po[7] && !(kn.dbg & (8 | 268435456))) {
+        if (po[8] > po[7] && !(kn.dbg & (DBG_SCALAR_WALK | DBG_NO_TRACK_PLANS))) {
             TrackArgs TA;
             memset(&TA, 0, sizeof(TA));
             TA.go_starts = (const i64 *)ld->st.geno_o_starts; TA.go_stops = (const i64 *)ld->st.geno_o_stops;
             TA.geno_v_idxs = ld->st.geno_v_idxs; TA.v_starts = ld->st.v_starts; TA.ilens = ld->st.ilens; TA.n_variants = ld->st.n_variants;
-            TA.grec = (debug_flags() & 16) ? nullptr : ld->st.geno_rec;
+            TA.grec = (debug_flags() & DBG_NO_GENO_REC) ? nullptr : ld->st.geno_rec;
             TA.regions = t_regions; TA.regions_stride = 4; TA.shifts = t_shifts; TA.geno_offset_idx = t_goi;
             TA.n_rows = n_used * c.ploidy; TA.ploidy = (int)c.ploidy; TA.ploidy_shift = log2_exact(c.ploidy);
             int chunks = 1;
@@ -1597,7 +1583,7 @@ int gvl_loader_start_epoch(gvl_loader *ld, const int64_t *order, int64_t n, int3
         ld->e_seeds = (u64 *)(base + po[4]);
         ld->e_track_offsets = (i64 *)(base + po[5]);
         ld->e_out_offsets = (i64 *)(base + po[6]);
-        ld->e_hplan = (loader_hap_plan_bytes(&c, n, kn) > 0 && !(kn.dbg & 536870912)) ? base + po[8] : nullptr;
+        ld->e_hplan = (loader_hap_plan_bytes(&c, n, kn) > 0 && !(kn.dbg & DBG_NO_HAP_PLANS)) ? base + po[8] : nullptr;
         ld->e_rag_offs = loader_epoch_sizing(&ld->st, &c, kn) ? (i64 *)(base + po[9]) : nullptr;
         {
             const i64 nb_used = drop_last ? n / c.batch_size : (n + c.batch_size - 1) / c.batch_size;
@@ -1608,7 +1594,7 @@ int gvl_loader_start_epoch(gvl_loader *ld, const int64_t *order, int64_t n, int3
         int cl = 0;
         ld->e_chunks = 1;
         if (wsb > 0) (void)pick_chunk(c.output_length, &ld->e_chunks, &cl);
-        const bool planned = wsb > 0 && !(kn.dbg & (8 | 268435456));
+        const bool planned = wsb > 0 && !(kn.dbg & (DBG_SCALAR_WALK | DBG_NO_TRACK_PLANS));
         // (the table was filled for n_used = every query of a whole batch, or all n: the plan's two parts are laid out for that many rows)
         const i64 n_used_rows = (drop_last ? (n / c.batch_size) * c.batch_size : n) * c.ploidy;
         ld->e_plan_hdr = planned ? (int2 *)(base + po[7]) : nullptr;
@@ -1695,7 +1681,7 @@ static int loader_submit(gvl_loader *ld, i64 g) {
         if (loader_ragged(&c)) {
             // row lengths and offsets on the device (rows cut to the slot's capacity are reported, never silent);
             // the reconstruct launch below then reads them -- no host round trip.  One sizing per GROUP (below) unless the
-            // dataset's rows take the wave-per-row length kernel (or GVL_DBG & 134217728: per batch, as before round 4)
+            // dataset's rows take the wave-per-row length kernel (or DBG_RAGGED_PER_BATCH: per batch, as before round 4)
             if (ld->e_rag_offs) {
                 // sized with the epoch's table: the launch reads its rows' offsets THERE (nothing in front of it); the consumer's
                 // copies go to the slots behind it
@@ -1704,7 +1690,7 @@ static int loader_submit(gvl_loader *ld, i64 g) {
                 oc.out_offsets = nullptr;
                 continue;
             }
-            if (loader_long_rows(&ld->st, ld->cur_kn) || (ld->cur_kn.dbg & 134217728)) {
+            if (diffs_long_rows(&ld->st, ld->cur_kn.dbg) || (ld->cur_kn.dbg & DBG_RAGGED_PER_BATCH)) {
                 const int rc0 = hap_offsets_impl(&ld->st, &bt, nullptr, o.out_offsets, o.sizes, c.max_row_len, s);
                 if (rc0) return rc0;
             } else {
@@ -1757,8 +1743,8 @@ static int loader_submit(gvl_loader *ld, i64 g) {
             (void)traced("launch tracks", [&] {
                 rc = tracks_batch_impl(&ld->st, &bts[m], (const int64_t *)o.idx, ld->tracks, c.n_tracks, par, c.strategy_id, c.track_seed,
                                        (const u64 *)o.track_seed, o.tracks, K * c.output_length, base + ld->part[10], c.scratch_stride, s,
-                                       (debug_flags() & 131072) ? nullptr : ld->e_track_offsets + j * (c.batch_size + 1),
-                                       (debug_flags() & 131072) ? nullptr : ld->e_out_offsets,
+                                       (debug_flags() & DBG_TRACK_SIZING_PER_BATCH) ? nullptr : ld->e_track_offsets + j * (c.batch_size + 1),
+                                       (debug_flags() & DBG_TRACK_SIZING_PER_BATCH) ? nullptr : ld->e_out_offsets,
                                        ld->e_plan_hdr ? ld->e_plan_hdr + j * c.batch_size * c.ploidy * (i64)ld->e_chunks : nullptr,
                                        ld->e_plan_ent ? ld->e_plan_ent + j * c.batch_size * c.ploidy * (i64)PLAN_MAXE : nullptr);
                 return hipSuccess;

@@ -55,11 +55,49 @@ constexpr int HP_STRIDE_DW = 4 + 8 * HP_ENT + 2 * HP_ENT;
 constexpr int HP_MAX_CHUNKS = 512;           // rows of more chunks are not planned (a wave's LDS tables)
 inline i64 hap_plan_bytes(i64 n_rows, i64 chunks) { return n_rows * chunks * (i64)HP_STRIDE_DW * 4; }
 
-// Timing ablations -- GVL_DBG bits 1 / 2 / 4 (no variants / no stores / no loads), 262144 / 524288 (the lean kernel without re-alignment /
-// allele bytes: WRONG output for rows with indels) and 8388608 / 16777216 (realign_tracks_kernel stops early: NO output) -- exist in
-// -DGVL_DIAG builds only (tools/ablate.sh builds one next to the shipped library).  The shipped library masks them off on the host
-// (debug_flags) and compiles their tests out of the kernels (GVL_ABL(x) = 0): it has no mode that returns wrong bytes.
-constexpr int DBG_ABLATIONS = 1 | 2 | 4 | 262144 | 524288 | 8388608 | 16777216;
+// GVL_DBG bits (the environment's value, or gvl_set_debug_flags): test and diagnostic switches, most of which take away one way
+// a row can reach its output so that the GPU suite can be run down every path.  The values are ABI: tests, tools and the Python
+// layer pass them as integers.
+enum DbgBit : int {
+    DBG_ABL_NO_VARIANTS  = 1,           // [ablation] every row as if it had no variants
+    DBG_ABL_NO_STORES    = 2,           // [ablation] no output stores
+    DBG_ABL_NO_LOADS     = 4,           // [ablation] no reference loads
+    DBG_SCALAR_WALK      = 8,           // every row through the scalar walk (haplotypes and tracks); no track row plans
+    DBG_NO_GENO_REC      = 16,          // ignore gvl_static.geno_rec (records come from geno_v_idxs -> vrec)
+    DBG_NO_SNP_PLAN      = 32,          // no scan-free plan for SNP-only rows (they join the packed plan)
+    DBG_NO_SLOT_REC      = 64,          // ignore gvl_static.slot_rec (rows find their records through the CSR)
+    DBG_NO_SPEC_REF      = 128,         // no speculative reference reads in front of the plan
+    DBG_NO_FRONT         = 256,         // a mixed ragged launch's long rows by the wave that meets them, chunk after chunk (no front
+                                        // workgroups: lean_solo_rows' crews); all-purpose kernel: its per-workgroup time stamps
+    DBG_NO_PACKABLE      = 512,         // no packable rows at all (every row runs the per-wave scans)
+    DBG_NO_BUCKET_INDEX  = 1024,        // the painter ignores the per-list bucket index (exact 64-ary searches per chunk)
+    DBG_DIFFS_WAVE_ROWS  = 2048,        // length deltas (get_diffs_sparse, ragged sizing) always one wave per row
+    DBG_PAINT_TIMELINE   = 4096,        // the painter records its per-phase time stamps (gvl_diag_set_stamps)
+    DBG_PAINT_LDS_IMAGE  = 8192,        // the painter always paints an LDS image (no start-bitmap lookup for non-overlapping candidates)
+    DBG_NO_LEAN          = 16384,       // no lean kernel: the all-purpose kernel over every row (tested through the route masks only)
+    DBG_LEAN_SOLO        = 32768,       // the lean kernels hand EVERY row to their solo general path (per-wave scans from the byte reference)
+    DBG_NO_REALIGN_LDS   = 65536,       // the lean kernels re-read the runs of a row with indels from memory (no re-alignment in LDS)
+    DBG_TRACK_SIZING_PER_BATCH = 131072,    // the native loop sizes the scratch tracks per batch (not once per epoch)
+    DBG_ABL_NO_REALIGN   = 262144,      // [ablation] the lean kernel without re-alignment (WRONG output for rows with indels)
+    DBG_ABL_NO_ALLELES   = 524288,      // [ablation] the lean kernel without allele bytes, and no scan plan (WRONG output for indels)
+    DBG_NO_LEAN_LONG     = 1048576,     // rows longer than one chunk never take the lean kernel: the all-purpose kernel
+    DBG_NO_REALIGN_WINDOW = 2097152,    // realignment from intervals never uses its window (every value looked up in the interval list)
+    DBG_NO_FUSED_TRACKS  = 4194304,     // tracks are always painted into the scratch track first (no realignment straight from intervals)
+    DBG_ABL_TRACK_WALK   = 8388608,     // [ablation] realign_tracks_kernel stops behind the walk (NO output)
+    DBG_ABL_TRACK_WINDOW = 16777216,    // [ablation] realign_tracks_kernel stops behind the window build (NO output)
+    DBG_PIPE_ALWAYS      = 33554432,    // rows of one chunk always take the pipelined kernel, with as few workgroups as 32 rows per wave allow
+    DBG_PIPE_NEVER       = 67108864,    // rows of one chunk never take the pipelined kernel (nor its channel-major / annotated / keep-mask forms)
+    DBG_RAGGED_PER_BATCH = 134217728,   // the native loop sizes ragged rows per batch (not per epoch or group)
+    DBG_NO_TRACK_PLANS   = 268435456,   // no track row plans (track_plan_kernel): every chunk-wave walks its row itself
+    DBG_NO_HAP_PLANS     = 536870912,   // rows of several chunks go without chunk plans (hap_plan_kernel): every chunk-wave walks its row
+    DBG_ROUND4_ROUTES    = 1073741824,  // round 4's routing of the other output modes: channel-major one-hot, keep masks, annotations,
+                                        // get_reference and the fast track kernel run the all-purpose (general) kernel
+};
+// The [ablation] bits change the output: they exist in -DGVL_DIAG builds only (tools/ablate.sh builds one next to the shipped
+// library).  The shipped library masks them off on the host (debug_flags) and compiles their tests out of the kernels
+// (GVL_ABL(x) = 0): it has no mode that returns wrong bytes.
+constexpr int DBG_ABLATIONS = DBG_ABL_NO_VARIANTS | DBG_ABL_NO_STORES | DBG_ABL_NO_LOADS | DBG_ABL_NO_REALIGN | DBG_ABL_NO_ALLELES |
+                              DBG_ABL_TRACK_WALK | DBG_ABL_TRACK_WINDOW;
 #ifdef GVL_DIAG
 #define GVL_ABL(x) (x)
 #else
@@ -178,6 +216,7 @@ int fill_diff_args(DiffArgs &D, const gvl_static *st, const gvl_batch *bt, const
 int launch_recon(const ReconArgs &A, int chunks, int variant, void *stream);
 hipError_t pool_alloc(void **p, size_t bytes, hipStream_t s);      // stream-ordered scratch from the library's own pool (free: hipFreeAsync)
 // gvl_lean.hip
+void fill_lean_args(LeanArgs &A, const ReconArgs &RA, int chunks);     // (memset first)
 int launch_lean(const ReconArgs &RA, int chunks, void *stream);
 int launch_hap_plan(const ReconArgs &RA, int chunks, u32 *plan, void *stream);
 // gvl_lean_pipe.hip

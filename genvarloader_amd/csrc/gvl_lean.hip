@@ -8,7 +8,7 @@ namespace {
 }  // namespace
 
 namespace gvli {
-static void fill_lean_args(LeanArgs &A, const ReconArgs &RA, int chunks) {
+void fill_lean_args(LeanArgs &A, const ReconArgs &RA, int chunks) {
     memset(&A, 0, sizeof(A));
     A.ref4 = RA.ref4; A.ref_offsets = RA.ref_offsets; A.srec = RA.srec;
     A.regions = RA.regions; A.shifts = RA.shifts; A.geno_offset_idx = RA.geno_offset_idx; A.to_rc = RA.to_rc;
@@ -37,11 +37,11 @@ int launch_hap_plan(const ReconArgs &RA, int chunks, u32 *plan, void *stream) {
 int launch_lean(const ReconArgs &RA, int chunks, void *stream) {
     LeanArgs A;
     fill_lean_args(A, RA, chunks);
-    // the rows' chunk plans, when the caller brings them (gvl_batch.hap_plan: made once per epoch by the native loader; GVL_DBG &
-    // 536870912: ignored).  A stand-alone launch does NOT make them for itself: measured (profiles/r05_cfg4_plans.txt), the
+    // the rows' chunk plans, when the caller brings them (gvl_batch.hap_plan: made once per epoch by the native loader; DBG_NO_HAP_PLANS:
+    // ignored).  A stand-alone launch does NOT make them for itself: measured (profiles/r05_cfg4_plans.txt), the
     // planner in front of every launch costs more than the walks it saves (7 us + a stream-ordered allocation against 2.7 us)
     const bool ann = chunks > 1 && RA.av && RA.ap;
-    if (chunks > 1 && !RA.out_offsets && chunks <= HP_MAX_CHUNKS && !(debug_flags() & 536870912)) A.hplan = RA.hplan;
+    if (chunks > 1 && !RA.out_offsets && chunks <= HP_MAX_CHUNKS && !(RA.dbg & DBG_NO_HAP_PLANS)) A.hplan = RA.hplan;
     // rows of several chunks: a wave takes `sub` consecutive chunks.  Without plans 2 -- the second chunk resumes the first one's
     // walk; BASELINE config 4's 256 rows x 64 chunks are then 8 192 waves, every wave slot of the part once --, with plans 1: there
     // is no walk to share, and 16 384 short waves start their reads under each other's stores (34.9 against 37.6 us,

@@ -72,7 +72,7 @@ __device__ __noinline__ __attribute__((noreturn)) void lean_solo_row(
         o_s = A.go_starts[oidx];
         const i64 nv = A.go_stops[oidx] - o_s;
         n_var = nv < 0 ? 0 : (nv > 0x7FFFFFFFll ? 0x7FFFFFFF : (int)nv);
-        if (A.dbg & GVL_ABL(1)) n_var = 0;
+        if (A.dbg & GVL_ABL(DBG_ABL_NO_VARIANTS)) n_var = 0;
     }
     if (lane == 0) {
         RowIn ri;
@@ -123,7 +123,7 @@ __device__ __noinline__ __attribute__((noreturn)) void lean_solo_row_at(
         o_s = A.go_starts[oidx];
         const i64 nv = A.go_stops[oidx] - o_s;
         n_var = nv < 0 ? 0 : (nv > 0x7FFFFFFFll ? 0x7FFFFFFF : (int)nv);
-        if (A.dbg & GVL_ABL(1)) n_var = 0;
+        if (A.dbg & GVL_ABL(DBG_ABL_NO_VARIANTS)) n_var = 0;
     }
     if (lane == 0) {
         RowIn ri;
@@ -412,10 +412,10 @@ __global__ __launch_bounds__(LEAN_THREADS) __attribute__((amdgpu_waves_per_eu(8,
     if constexpr (!LONG) {
         const i64 R64e = c_e - c_s;
         const bool row_e = c_ok && o_ok && l_start >= 0 && l_start < (1 << 30) && l_shift >= 0 && l_shift < (1 << 30) &&
-                           R64e >= 0 && R64e < (1ll << 31) && !(A.dbg & 32768);
+                           R64e >= 0 && R64e < (1ll << 31) && !(A.dbg & DBG_LEAN_SOLO);
         const int r0e = l_start + l_shift;
         const u32 G0e = (u32)c_s + (u32)r0e;
-        if (row_e && (i64)r0e + Lrow <= R64e && !(A.dbg & GVL_ABL(4))) {
+        if (row_e && (i64)r0e + Lrow <= R64e && !(A.dbg & GVL_ABL(DBG_ABL_NO_LOADS))) {
             const u8 *wb = A.ref4 + (G0e >> 1) + 4u * (u32)lane;
 #pragma unroll
             for (int s = 0; s < LEAN_STEPS; ++s)
@@ -461,7 +461,7 @@ __global__ __launch_bounds__(LEAN_THREADS) __attribute__((amdgpu_waves_per_eu(8,
     // reference < 2^32 (the host checks ref_len) -------------------------------------------------------
     const i64 R64 = c_e - c_s;
     bool lean_row = c_ok && o_ok && l_start >= 0 && l_start < (1 << 30) && l_shift >= 0 && l_shift < (1 << 30) &&
-                    R64 >= 0 && R64 < (1ll << 31) && !(A.dbg & 32768) && !too_long;
+                    R64 >= 0 && R64 < (1ll << 31) && !(A.dbg & DBG_LEAN_SOLO) && !too_long;
     // (padded_slice, src/reference/mod.rs:9-50: start >= stop leaves the row untouched, a stop behind the contig pads: not this path's rows)
     if (ref_only) lean_row = lean_row && l_start < l_end && (i64)l_end <= R64;
     const int R = (int)R64;
@@ -477,7 +477,7 @@ __global__ __launch_bounds__(LEAN_THREADS) __attribute__((amdgpu_waves_per_eu(8,
     // (LONG: the same reads, issued once the walk has told where the chunk's window is.)
     u64 xw[LEAN_STEPS], xw_tail = 0;
     auto issue_window = [&]() {
-        if (spec_ok && !(A.dbg & GVL_ABL(4))) {
+        if (spec_ok && !(A.dbg & GVL_ABL(DBG_ABL_NO_LOADS))) {
             const u8 *wb = A.ref4 + (G0 >> 1) + 4u * (u32)lane;
 #pragma unroll
             for (int s = 0; s < LEAN_STEPS; ++s)
@@ -525,7 +525,7 @@ __global__ __launch_bounds__(LEAN_THREADS) __attribute__((amdgpu_waves_per_eu(8,
             const int last = 63 - __builtin_clzll(m_ins);
             pb_total = OpSat::f(rdl(pb_first, last), rdl(alen0, last) - 1);
             const u8 *src = allele_byte_of(lane < pb_total ? lane : 0, pb_owner, pb_i);      // (every lane: it shuffles between lanes)
-            if (lane < pb_total && !(A.dbg & GVL_ABL(4))) pb_v = (u32)*src;
+            if (lane < pb_total && !(A.dbg & GVL_ABL(DBG_ABL_NO_LOADS))) pb_v = (u32)*src;
         }
     };
     // ---- plan: which variants are applied, where their alleles start in the row (the indel shift), and the
@@ -812,7 +812,7 @@ __global__ __launch_bounds__(LEAN_THREADS) __attribute__((amdgpu_waves_per_eu(8,
         m_ins = lean_row ? __builtin_amdgcn_ballot_w64(valid && alen0 > 1) : 0;
         issue_allele_bytes();
 
-        if (lean_row && (m_plain == 0 || (A.dbg & GVL_ABL(524288)))) {
+        if (lean_row && (m_plain == 0 || (A.dbg & GVL_ABL(DBG_ABL_NO_ALLELES)))) {
             // SNPs only, distinct positions inside the contig: whichever way the shift completes (:115-146) or runs
             // out (:200-205) ref_idx lands on ref_start + shift; SNP i sits at pos_i - r0 iff that is inside the row
             a_out = pos - r0;
@@ -919,7 +919,7 @@ __global__ __launch_bounds__(LEAN_THREADS) __attribute__((amdgpu_waves_per_eu(8,
     u32 *const row = rows[wave];
     // (LONG: an indel at or in front of the chunk's first base is already in d_init)
     const u64 m_ns = __builtin_amdgcn_ballot_w64(nonsnp && (!LONG || a_out > 0));
-    const bool respec = !(m_ns == 0 && d_init == G0 && spec_ok) && !(A.dbg & GVL_ABL(262144));     // (not the one run that was read speculatively)
+    const bool respec = !(m_ns == 0 && d_init == G0 && spec_ok) && !(A.dbg & GVL_ABL(DBG_ABL_NO_REALIGN));     // (not the one run that was read speculatively)
     u32 x[LEAN_STEPS];
     if (!respec) {
         LEAN_NOTE(8, 0);
@@ -935,7 +935,7 @@ __global__ __launch_bounds__(LEAN_THREADS) __attribute__((amdgpu_waves_per_eu(8,
         // bases apart could share a lane's 8 bases (a lane handles ONE run boundary).
         const int n_dw = (L + 7) >> 3;               // dwords of the row; the tail sits right behind them
         const int rho0 = (int)(d_init - G0);
-        bool in_win = spec_ok && rho0 >= 0 && rho0 <= LEAN_TAIL && !(A.dbg & 65536);
+        bool in_win = spec_ok && rho0 >= 0 && rho0 <= LEAN_TAIL && !(A.dbg & DBG_NO_REALIGN_LDS);
         {
             int a_prev = -8;
             for (u64 m = m_ns; m; m &= m - 1) {
@@ -1032,7 +1032,7 @@ __global__ __launch_bounds__(LEAN_THREADS) __attribute__((amdgpu_waves_per_eu(8,
 #pragma unroll
             for (int s = 0; s < LEAN_STEPS; ++s) {
                 y[s] = 0; z[s] = 0; cuts[s] = 8;
-                if (s * 512 < L && !(A.dbg & GVL_ABL(4))) {
+                if (s * 512 < L && !(A.dbg & GVL_ABL(DBG_ABL_NO_LOADS))) {
                     u32 lo_d, hi_d; bool multi;
                     runs_of(s * 512 + q_lane, lo_d, hi_d, cuts[s], multi);
                     bool mixed_lo, mixed_hi;
@@ -1060,7 +1060,7 @@ __global__ __launch_bounds__(LEAN_THREADS) __attribute__((amdgpu_waves_per_eu(8,
                                 if (q + i >= rdl(a_out, j)) dd = (u32)rdl((int)dv, j);
                             }
                             const u32 p = clampp((u32)(q + i) + dd);
-                            const u32 b = (A.dbg & GVL_ABL(4)) ? 0u : (u32)A.ref4[p >> 1];
+                            const u32 b = (A.dbg & GVL_ABL(DBG_ABL_NO_LOADS)) ? 0u : (u32)A.ref4[p >> 1];
                             v |= ((b >> (4u * (p & 1u))) & 0xFu) << (4 * i);
                         }
                         x[s] = v;     // (x[] is indexed by a loop variable here: rare path, the spill is its own)
@@ -1077,7 +1077,7 @@ __global__ __launch_bounds__(LEAN_THREADS) __attribute__((amdgpu_waves_per_eu(8,
 
     // ---- phase B: SNPs and allele bytes ---------------------------------------------------------------------
     if (applied && w_i > 0 && skip_l == 0 && (!LONG || a_out >= 0)) row_set_nibble(row, a_out, ref4_nibble(inl));      // an allele's first byte is inline
-    if (m_ins && !(A.dbg & GVL_ABL(262144))) {
+    if (m_ins && !(A.dbg & GVL_ABL(DBG_ABL_NO_REALIGN))) {
         // byte i (>= 1) of variant j's allele lands at a_out_j + i - skip_j if the variant is applied and the byte is
         // among the w_j the row has room for
         auto place = [&](const int t, const int owner, const int i, const u32 b) {
@@ -1163,7 +1163,7 @@ __global__ __launch_bounds__(LEAN_THREADS) __attribute__((amdgpu_waves_per_eu(8,
     };
     if constexpr (CL) {
         // channel-major: plane c of row k at onehot + (4 k + c) Lrow; the chunk's bases at the same offset of every plane
-        if (!(A.dbg & GVL_ABL(2))) {
+        if (!(A.dbg & GVL_ABL(DBG_ABL_NO_STORES))) {
             u8 *const cl_base = A.onehot + (i64)k * 4 * Lrow + (rc ? Lrow - lo - L : lo);
             (void)stream_onehot_cl<LEAN_MAX_TRIPS * TRIP>(row, lut, tbase, rc, L, (i64)Lrow, cl_base, lane);
             if (HAPS) {
@@ -1177,7 +1177,7 @@ __global__ __launch_bounds__(LEAN_THREADS) __attribute__((amdgpu_waves_per_eu(8,
                 }
             }
         }
-    } else if ((L & (4 * TRIP - 1)) == 0 && !(A.dbg & GVL_ABL(2))) {
+    } else if ((L & (4 * TRIP - 1)) == 0 && !(A.dbg & GVL_ABL(DBG_ABL_NO_STORES))) {
         stream4(0);
         if (L > 4 * TRIP) stream4(4);
     } else if constexpr (RAGL) {
@@ -1185,7 +1185,7 @@ __global__ __launch_bounds__(LEAN_THREADS) __attribute__((amdgpu_waves_per_eu(8,
         // of a reverse-complemented one -- then the last L & 3 bases dword by dword / byte by byte, by the lane that owns their
         // group (a reverse-complemented chunk's are its FIRST bases): recon_lean_rows_kernel's ragged phase C
         const int fg = L >> 2, rem = L & 3;
-        if (!(A.dbg & GVL_ABL(2))) {
+        if (!(A.dbg & GVL_ABL(DBG_ABL_NO_STORES))) {
 #pragma unroll
             for (int u = 0; u < LEAN_MAX_TRIPS; ++u) {
                 if (u * WAVE < fg || (rem > 0 && u * WAVE == fg)) {
@@ -1229,7 +1229,7 @@ __global__ __launch_bounds__(LEAN_THREADS) __attribute__((amdgpu_waves_per_eu(8,
             if (u * TRIP < L) {
                 const u32 r = row16[u * WAVE + lane];
                 const u32 rr = __builtin_amdgcn_perm(0u, r, sel);
-                if (u * TRIP + (int)lane4 < L && !(A.dbg & GVL_ABL(2))) {
+                if (u * TRIP + (int)lane4 < L && !(A.dbg & GVL_ABL(DBG_ABL_NO_STORES))) {
                     if (OH) {
                         const uint2 a = lut[tbase + (rr & 0xFFu)], b = lut[tbase + (rr >> 8)];
                         u32x4_a4 o = {a.x, a.y, b.x, b.y};
@@ -1248,7 +1248,7 @@ __global__ __launch_bounds__(LEAN_THREADS) __attribute__((amdgpu_waves_per_eu(8,
         // bases carry their own coordinate, allele bytes their variant's index and position).  Forward position p of the chunk lies in the
         // allele of entry j iff a_out_j <= p < a_out_j + w_j, else in the reference run behind the last indel at or in front of it.  A lane
         // takes four consecutive output positions per trip; a reverse-complemented row's annotations are reversed (src/reverse.rs:25-38).
-        if (!(A.dbg & GVL_ABL(2))) {
+        if (!(A.dbg & GVL_ABL(DBG_ABL_NO_STORES))) {
             int *const av_row = A.av + row0, *const ap_row = A.ap + row0;
             const u64 m_app = __builtin_amdgcn_ballot_w64(applied && w_i > 0);
             const u64 m_nsa = __builtin_amdgcn_ballot_w64(nonsnp);
@@ -1343,7 +1343,7 @@ __global__ __launch_bounds__(LEAN_THREADS) void hap_plan_kernel(const LeanArgs A
     const i64 R64 = c_e - c_s;
     const u32 cs32 = (u32)c_s;
     bool ok = c_ok && o_ok && l_start >= 0 && l_start < (1 << 30) && l_shift >= 0 && l_shift < (1 << 30) && R64 >= 0 && R64 < (1ll << 31) &&
-              !(A.dbg & 32768) && A.grec != nullptr && nv64 >= 0 && nv64 < (1ll << 30);
+              !(A.dbg & DBG_LEAN_SOLO) && A.grec != nullptr && nv64 >= 0 && nv64 < (1ll << 30);
     const int n_var = ok ? (int)nv64 : 0;
     wave_lds_fence();
 

@@ -31,18 +31,10 @@ int launch_lean_rows(const ReconArgs *RAs, int n, void *stream, int rag_chunks) 
     const ReconArgs &RA = RAs[0];
     LeanArgs A;
     LeanMany M;
-    memset(&A, 0, sizeof(A));
+    fill_lean_args(A, RA, 1);
     memset(&M, 0, sizeof(M));
-    A.ref4 = RA.ref4; A.ref_offsets = RA.ref_offsets; A.srec = RA.srec;
-    A.regions = RA.regions; A.shifts = RA.shifts; A.geno_offset_idx = RA.geno_offset_idx; A.to_rc = RA.to_rc;
-    A.onehot = RA.onehot; A.haps = RA.haps; A.out_offsets_w = RA.out_offsets_w; A.alt_alleles = RA.alt_alleles;
-    A.go_starts = RA.go_starts; A.go_stops = RA.go_stops; A.grec = RA.grec; A.alt_offsets = RA.alt_offsets;
-    A.n_geno_offsets = RA.n_geno_offsets;
-    A.n_contigs = RA.n_contigs; A.regions_stride = (int)RA.regions_stride;
-    A.ploidy_shift = RA.ploidy_shift; A.ploidy = RA.ploidy; A.L = (int)RA.fixed_len; A.dbg = RA.dbg;
-    A.chunks = 1; A.sub = 1;
-    A.ref_only = RA.ref_only;
-    A.slot_vidx = RA.slot_vidx;
+    A.stamps = nullptr; A.keep = nullptr; A.keep_offsets = nullptr; A.av = nullptr; A.ap = nullptr;   // (keep masks, annotations: per batch, LeanMany)
+    A.sub = 1; A.slot_vidx = RA.slot_vidx;
     A.rows_per_batch = (int)RA.n_rows; A.n_batches = n;
     A.max_row_len = (int)((i64)RA.chunk_len * (RA.out_offsets ? rag_chunks : 1));
     i64 total = 0, longest = 0;
@@ -74,20 +66,20 @@ int launch_lean_rows(const ReconArgs *RAs, int n, void *stream, int rag_chunks) 
     if (x100 < 100) x100 = total >= 49152 ? 150 : 100;
     if (x100 > 100 * (i64)PIPE_MAX_ROWS) x100 = 100 * (i64)PIPE_MAX_ROWS;      // (a wave's deferred-rows mask has a bit per row)
     i64 waves = (total * 100 + x100 - 1) / x100;
-    if (debug_flags() & 33554432) {
+    if (RA.dbg & DBG_PIPE_ALWAYS) {
         i64 rpw = (total + LEAN_WAVES - 1) / LEAN_WAVES;
         rpw = rpw > PIPE_MAX_ROWS ? PIPE_MAX_ROWS : (rpw < 1 ? 1 : rpw);
         waves = (total + rpw - 1) / rpw;
     }
     // ragged rows beyond the streaming loop's trips (the caller's bound says there may be some): one front workgroup per 256 rows finds
-    // them and runs their chunks in parallel (lean_solo_rows' crews); GVL_DBG & 256: by the wave that meets them, as before
+    // them and runs their chunks in parallel (lean_solo_rows' crews); DBG_NO_FRONT: by the wave that meets them, as before
     // (several batches: the LARGEST bound any of them gave decides)
-    if (RA.out_offsets && longest > PIPE_RAG_MAXT * TRIP && !(debug_flags() & 256)) A.front = (int)((total + LEAN_THREADS - 1) / LEAN_THREADS);
+    if (RA.out_offsets && longest > PIPE_RAG_MAXT * TRIP && !(RA.dbg & DBG_NO_FRONT)) A.front = (int)((total + LEAN_THREADS - 1) / LEAN_THREADS);
     const unsigned grid = (unsigned)((waves + LEAN_WAVES - 1) / LEAN_WAVES) + (unsigned)A.front;
     const dim3 g(grid), b(LEAN_THREADS);
     hipStream_t s = (hipStream_t)stream;
-    // (launches without a keep mask that are not gvl_get_reference's: the forms with both compiled out; GVL_DBG & 1073741824 keeps the general ones)
-    bool km = A.ref_only != 0 || (A.dbg & 1073741824);
+    // (launches without a keep mask that are not gvl_get_reference's: the forms with both compiled out; DBG_ROUND4_ROUTES keeps the general ones)
+    bool km = A.ref_only != 0 || (A.dbg & DBG_ROUND4_ROUTES);
     for (int i = 0; i < n; ++i) km = km || RAs[i].keep != nullptr || RAs[i].keep_offsets != nullptr;
     if (RA.av && RA.ap) {          // annotated haplotypes: bytes + the two annotation streams
         if (RA.out_offsets && A.onehot) recon_lean_rows_kernel<true, true, true, false, true><<<g, b, 0, s>>>(A, RA, M);

@@ -203,7 +203,7 @@ __device__ __noinline__ __attribute__((noreturn)) void lean_solo_rows(
             o_s = rfl64(A.go_starts[l_oidx]);
             const i64 nv = rfl64(A.go_stops[l_oidx]) - o_s;
             n_var = nv < 0 ? 0 : (nv > 0x7FFFFFFFll ? 0x7FFFFFFF : (int)nv);
-            if (A.dbg & GVL_ABL(1)) n_var = 0;
+            if (A.dbg & GVL_ABL(DBG_ABL_NO_VARIANTS)) n_var = 0;
         }
         if (lane == 0) {
             RowIn ri;
@@ -425,7 +425,7 @@ __global__ __launch_bounds__(LEAN_THREADS) __attribute__((amdgpu_waves_per_eu(8,
         }
         // the lean path's rows: inside their contig, 30-bit coordinates, and the window readable without padding
         r.ok = c_ok && o_ok && len_ok && r.l_start >= 0 && r.l_start < (1 << 30) && r.l_shift >= 0 && r.l_shift < (1 << 30) &&
-               r.R >= 0 && (i64)r0 + r.L <= (i64)r.R && !(ka->dbg & 32768);
+               r.R >= 0 && (i64)r0 + r.L <= (i64)r.R && !(ka->dbg & DBG_LEAN_SOLO);
         // (padded_slice, src/reference/mod.rs:9-50: start >= stop leaves the row untouched, a stop behind the contig pads: not this path's rows)
         if (ref_only) r.ok = r.ok && r.l_start < l_end && l_end <= r.R;
         r.G0 = r.cs32 + (u32)r0;
@@ -461,10 +461,10 @@ __global__ __launch_bounds__(LEAN_THREADS) __attribute__((amdgpu_waves_per_eu(8,
             const u8 *win = ka->ref4 + a0;
             const u8 *s1 = lane < GVL_SLOT_RECS ? reinterpret_cast<const u8 *>(ka->srec + (l_oidx * GVL_SLOT_RECS + lane))
                                                 : win + 16 * (lane - GVL_SLOT_RECS);
-            if (lane < GVL_SLOT_RECS ? !ref_only : !(ka->dbg & GVL_ABL(4))) glds_b128(s1, dst);      // (ref_only: no slot line)
+            if (lane < GVL_SLOT_RECS ? !ref_only : !(ka->dbg & GVL_ABL(DBG_ABL_NO_LOADS))) glds_b128(s1, dst);      // (ref_only: no slot line)
             const int need = (r.o_win + r.L + LEAN_TAIL + 16 + 1) >> 1;               // window bytes the row's picks may touch
             const int l2 = (need - PIPE_DMA1_WIN + 15) >> 4;                          // lanes of the second instruction
-            if (lane < l2 && lane < (CFG::WINB - PIPE_DMA1_WIN) / 16 && !(ka->dbg & GVL_ABL(4))) glds_b128(win + PIPE_DMA1_WIN + 16 * lane, dst + 1024u);
+            if (lane < l2 && lane < (CFG::WINB - PIPE_DMA1_WIN) / 16 && !(ka->dbg & GVL_ABL(DBG_ABL_NO_LOADS))) glds_b128(win + PIPE_DMA1_WIN + 16 * lane, dst + 1024u);
         }
         return r;
     };
@@ -714,7 +714,7 @@ __global__ __launch_bounds__(LEAN_THREADS) __attribute__((amdgpu_waves_per_eu(8,
         u32 x[CFG::STEPS];
         if (lean_row) {
             const int rho0 = (int)(d_init - G0);
-            bool in_win = rho0 >= 0 && rho0 <= LEAN_TAIL && !((ka->dbg & 65536) && m_ns != 0);
+            bool in_win = rho0 >= 0 && rho0 <= LEAN_TAIL && !((ka->dbg & DBG_NO_REALIGN_LDS) && m_ns != 0);
             if (m_ns == 0) {
                 // ONE run: every lane's 8 bases sit at the same offset from the window's start
                 const int off = rho0 + o_win;
@@ -888,7 +888,7 @@ __global__ __launch_bounds__(LEAN_THREADS) __attribute__((amdgpu_waves_per_eu(8,
                     const int s0 = rc ? Lr - 4 - hh : hh;                       // the first body group's first base (rc: may be < 0 when nb == 0)
                     const u32 sh = 4u * ((u32)s0 & 3u);
                     const int i0 = s0 >> 2;
-                    if (!(ka->dbg & GVL_ABL(2))) {
+                    if (!(ka->dbg & GVL_ABL(DBG_ABL_NO_STORES))) {
 #pragma unroll
                         for (int u = 0; u < CFG::MAXT; ++u) {
                             if (u * WAVE < nb) {
@@ -933,7 +933,7 @@ __global__ __launch_bounds__(LEAN_THREADS) __attribute__((amdgpu_waves_per_eu(8,
                     // channel-major planes: a lane takes 16 bases per step (two dwords of the nibble row), 1024 bases per wave-step;
                     // plane c of the row at oh_row + c * L; a reverse-complemented row's bases land mirrored, its channels swapped (the
                     // table's second half) and a lane's four dwords in reverse order
-                    if (!(ka->dbg & GVL_ABL(2))) {
+                    if (!(ka->dbg & GVL_ABL(DBG_ABL_NO_STORES))) {
                         n_after += stream_onehot_cl<CFG::MAXT * TRIP>(row, lut, tbase, rc, L, (i64)L, oh_row, lane);
                         if (HAPS) {
                             const i64 hp_lane = rc ? ((i64)L - 4 - 4 * (i64)lane) : 4 * (i64)lane;
@@ -980,7 +980,7 @@ __global__ __launch_bounds__(LEAN_THREADS) __attribute__((amdgpu_waves_per_eu(8,
                         if (HAPS) store_u32_unaligned(hap_row + hp_lane + (i64)(u0 + i) * hp_step, hb[i]);
                     }
                 };
-                if (!(ka->dbg & GVL_ABL(2))) {
+                if (!(ka->dbg & GVL_ABL(DBG_ABL_NO_STORES))) {
                     if ((L & (4 * TRIP - 1)) == 0) {
                         stream4(0);
                         if (L > 4 * TRIP) stream4(4);
@@ -1014,7 +1014,7 @@ __global__ __launch_bounds__(LEAN_THREADS) __attribute__((amdgpu_waves_per_eu(8,
                     // start}.  Stored like the ragged one-hot: groups of four counted from the output's first 64-byte boundary (fixed-length
                     // rows: from the row's start, which is one), head / tail positions one per lane; a reverse-complemented row's
                     // annotations are reversed (src/reverse.rs:25-38 on the i32 rows).
-                    if (!(ka->dbg & GVL_ABL(2))) {
+                    if (!(ka->dbg & GVL_ABL(DBG_ABL_NO_STORES))) {
                         int *const av_row = cur.av + row0, *const ap_row = cur.ap + row0;
                         const int hh0a = RAG ? (int)((RAG_HEAD - (int)(row0 & (RAG_HEAD - 1))) & (RAG_HEAD - 1)) : 0;
                         const int hha = hh0a < Lr ? hh0a : Lr;

@@ -54,7 +54,7 @@ __device__ __forceinline__ void recon_wave_scalar(const ReconArgs &A, const Luts
         o_s = rfl64(A.go_starts[o_idx]);
         const i64 nv = rfl64(A.go_stops[o_idx]) - o_s;
         n_var = nv < 0 ? 0 : (nv > 0x7FFFFFFFll ? 0x7FFFFFFF : (int)nv);
-        if (A.dbg & GVL_ABL(1)) n_var = 0;
+        if (A.dbg & GVL_ABL(DBG_ABL_NO_VARIANTS)) n_var = 0;
         if (has_keep) keep_off = rfl64(A.keep_offsets[k]);
     }
 
@@ -240,7 +240,7 @@ __device__ __forceinline__ void recon_wave_scalar(const ReconArgs &A, const Luts
             int av4[GROUP], ap4[GROUP];
             if (c_ok && c_next >= t_end && ((t_end - p0) & 3) == 0) {
                 // ---- uniform trip -------------------------------------------------
-                if (act && !(A.dbg & GVL_ABL(4))) wv = load_u32_unaligned(c_base + p0 + (u32)(GROUP * lane));
+                if (act && !(A.dbg & GVL_ABL(DBG_ABL_NO_LOADS))) wv = load_u32_unaligned(c_base + p0 + (u32)(GROUP * lane));
                 if (ANNOT) {
 #pragma unroll
                     for (int i = 0; i < GROUP; ++i) { av4[i] = -1; ap4[i] = c_apb + p + i; }
@@ -318,7 +318,7 @@ __device__ __forceinline__ void recon_wave_scalar(const ReconArgs &A, const Luts
                 np_pos = pc < npatch ? rdl(p_out, pc) : 0x7FFFFFFF;
             }
             // ---- stores ------------------------------------------------------------------
-            if (full && !(A.dbg & GVL_ABL(2))) {
+            if (full && !(A.dbg & GVL_ABL(DBG_ABL_NO_STORES))) {
                 // forward: jo = p; RC: jo = L - 4 - p.  In both cases jo = jo0 + lane_pos.
                 const int jo = (rc ? L - GROUP - p0 : p0) + lane_pos;
                 const u32 ww = __builtin_amdgcn_perm(0u, wv, rc_sel);
@@ -760,7 +760,7 @@ __device__ __forceinline__ void recon_body(const ReconArgs &A, ReconShared<ANNOT
     const int wave = rfl(tid >> 6);
     const int lo_clip = chunk * A.chunk_len;
     const bool has_keep = A.keep && A.keep_offsets;
-    const bool planned_ok = A.chunk_len <= CHUNK_TRIPS * TRIP && !(A.dbg & 8);
+    const bool planned_ok = A.chunk_len <= CHUNK_TRIPS * TRIP && !(A.dbg & DBG_SCALAR_WALK);
 
     GVL_STAMP(0);
     if (!SOLO && tid < 256) {  // LUTs
@@ -774,7 +774,7 @@ __device__ __forceinline__ void recon_body(const ReconArgs &A, ReconShared<ANNOT
     // 128-byte lines of the workgroup in ONE wave-load), all parked in LDS.  After the barrier no wave
     // needs a global read before its plan, so the reference bytes it requests next (below) stay in
     // flight behind nothing.
-    const bool use_srec = !SOLO && A.srec != nullptr && !A.ref_only && planned_ok && !(A.dbg & 512) && !ANNOT;
+    const bool use_srec = !SOLO && A.srec != nullptr && !A.ref_only && planned_ok && !(A.dbg & DBG_NO_PACKABLE) && !ANNOT;
     // wave 0's carry from P1a to P1b (the slot-line read stays in flight across the first barrier)
     i32x4 p1_rec = {0, 0, (int)GVL_SREC_EMPTY, 0};
     i64 p1_oidx = 0;
@@ -814,7 +814,7 @@ __device__ __forceinline__ void recon_body(const ReconArgs &A, ReconShared<ANNOT
         if (A.ref_only && (i64)l_start >= (i64)l_end) fl |= 4;                   // reference/mod.rs:16-18
         const bool shift_ok = !(ri.shift < 0 || ri.shift >= (1 << 30));
         if (!shift_ok || !planned_ok) fl |= 2;
-        if (use_srec && shift_ok && !(A.dbg & GVL_ABL(1))) fl |= 16;
+        if (use_srec && shift_ok && !(A.dbg & GVL_ABL(DBG_ABL_NO_VARIANTS))) fl |= 16;
         // a row longer than the caller's max_row_len hint would be left partly unwritten: report it
         if (row_lane && chunk == 0 && A.async_err && (i64)ri.L > (i64)gridDim.y * (i64)A.chunk_len) *A.async_err = 1;
         if (!row_lane || lo_clip >= ri.L) fl = 1;
@@ -851,9 +851,9 @@ __device__ __forceinline__ void recon_body(const ReconArgs &A, ReconShared<ANNOT
                 ri.o_s = l_gs;
                 const i64 nv = l_ge - l_gs;
                 ri.n_var = nv < 0 ? 0 : (nv > 0x7FFFFFFFll ? 0x7FFFFFFF : (int)nv);
-                if (A.dbg & GVL_ABL(1)) ri.n_var = 0;
+                if (A.dbg & GVL_ABL(DBG_ABL_NO_VARIANTS)) ri.n_var = 0;
             }
-            if (!(fl & 2) && ri.n_var <= 8 && !(A.dbg & 512)) fl |= 8;           // packable: planned with the other rows
+            if (!(fl & 2) && ri.n_var <= 8 && !(A.dbg & DBG_NO_PACKABLE)) fl |= 8;           // packable: planned with the other rows
         }
         ri.flags = fl;
         p1_fl = fl; p1_oidx = o_idx;
@@ -925,7 +925,7 @@ __device__ __forceinline__ void recon_body(const ReconArgs &A, ReconShared<ANNOT
     // speculative reference reads: on the slot-major path nothing between here and pass A waits for a
     // global load, so they stay in flight while the row is classified and planned.
     bool ell = (flags & 16) != 0 && packable;        // (tentative until P1b has seen the slot line)
-    const bool sp_on = g_ok && !(flags & 4) && !(A.dbg & (GVL_ABL(4) | 128)) && (ell || row_n_var == 0);
+    const bool sp_on = g_ok && !(flags & 4) && !(A.dbg & (GVL_ABL(DBG_ABL_NO_LOADS) | DBG_NO_SPEC_REF)) && (ell || row_n_var == 0);
     // lane u decides for trip u (full trips only), one ballot; the loads then differ by an immediate
     // offset only.  (The scalar unit is shared by the waves of a CU: per-trip scalar arithmetic in the
     // head of every wave is what this avoids.)
@@ -950,8 +950,8 @@ __device__ __forceinline__ void recon_body(const ReconArgs &A, ReconShared<ANNOT
     const bool spec_late = use_srec && wave == 0;
     if (!spec_late) issue_spec();
 #ifdef GVL_DIAG
-    // diagnostic (GVL_DBG 256): when do wave 1's speculative reference bytes arrive?  (stamp 15)
-    if (A.stamps && (A.dbg & 256) && wave == 1) {
+    // diagnostic (DBG_NO_FRONT): when do wave 1's speculative reference bytes arrive?  (stamp 15)
+    if (A.stamps && (A.dbg & DBG_NO_FRONT) && wave == 1) {
         __builtin_amdgcn_s_waitcnt(0);
         if (lane == 0) A.stamps[((u64)blockIdx.x * gridDim.y + blockIdx.y) * 16 + 15] = __builtin_amdgcn_s_memrealtime();
     }
@@ -1020,7 +1020,7 @@ __device__ __forceinline__ void recon_body(const ReconArgs &A, ReconShared<ANNOT
         const u64 m_slow = __builtin_amdgcn_ballot_w64(
             (f_valid && (d != 0 || alen != 1 || f_pos < 0 || (i64)f_pos + 1 > rfl64(ri.R))) ||
             (lane > 0 && rec_valid && f_pos == pos_prev));
-        is_fast = packable && m_slow == 0 && rs > -(1 << 30) && rs < (1 << 30) && !(A.dbg & 32);
+        is_fast = packable && m_slow == 0 && rs > -(1 << 30) && rs < (1 << 30) && !(A.dbg & DBG_NO_SNP_PLAN);
         // tell the workgroup: the slow flag, then one tick of the "decided" counter (meta[0].pad0_)
         if (lane == 0) {
             if (packable && !is_fast) meta[wave].slow = 1;
@@ -1481,7 +1481,7 @@ __device__ __forceinline__ void recon_body(const ReconArgs &A, ReconShared<ANNOT
                 for (int i = 0; i < GROUP; ++i) if (dd == (u32)i) av4[i] = pid;
             }
         }
-        if (full && !(A.dbg & GVL_ABL(2))) {
+        if (full && !(A.dbg & GVL_ABL(DBG_ABL_NO_STORES))) {
             const int jo = (rc ? L - GROUP - p0 : p0) + lane_pos;
             const u32 ww = __builtin_amdgcn_perm(0u, wv, rc_sel);
             const u32 b0_ = ww & 0xFF, b1_ = (ww >> 8) & 0xFF, b2_ = (ww >> 16) & 0xFF, b3_ = ww >> 24;
@@ -1567,7 +1567,7 @@ __device__ __forceinline__ void recon_body(const ReconArgs &A, ReconShared<ANNOT
         if (kind == K_REF || kind == K_ALLELE) {
             const u8 *arr = (kind == K_REF ? A.ref : A.alt_alleles) + seg_delta(lo, hi);
             u32 v = 0;
-            if (pred && !(A.dbg & GVL_ABL(4))) v = load_u32_unaligned(arr + p);
+            if (pred && !(A.dbg & GVL_ABL(DBG_ABL_NO_LOADS))) v = load_u32_unaligned(arr + p);
             return v;
         }
         return padb * 0x01010101u;
@@ -1634,7 +1634,7 @@ __device__ __forceinline__ void recon_body(const ReconArgs &A, ReconShared<ANNOT
             if ((todo >> u) & 1u) {
                 const u8 *src = reinterpret_cast<const u8 *>(((u64)(u32)rdl((int)d_ldhi, u) << 32) | (u32)rdl((int)d_ldlo, u));
                 wq[u] = 0;
-                if (lane4 < limit - (lo_clip + u * TRIP) && !(A.dbg & GVL_ABL(4))) wq[u] = load_u32_unaligned(src + (u32)lane4);
+                if (lane4 < limit - (lo_clip + u * TRIP) && !(A.dbg & GVL_ABL(DBG_ABL_NO_LOADS))) wq[u] = load_u32_unaligned(src + (u32)lane4);
             }
         }
     }
@@ -1782,7 +1782,7 @@ __device__ __forceinline__ void recon_body(const ReconArgs &A, ReconShared<ANNOT
                         for (int i = 0; i < GROUP; ++i) if (dd == (u32)i) av4[i] = pid;
                     }
                 }
-                if (lane4 < limit - p0 && !(A.dbg & GVL_ABL(2))) {
+                if (lane4 < limit - p0 && !(A.dbg & GVL_ABL(DBG_ABL_NO_STORES))) {
                     const i64 jo0 = (i64)(jo_base + u * jo_step);       // scalar
                     const u32 ww = __builtin_amdgcn_perm(0u, wv, rc_sel);
                     const u32 b0_ = ww & 0xFF, b1_ = (ww >> 8) & 0xFF, b2_ = (ww >> 16) & 0xFF, b3_ = ww >> 24;

@@ -53,25 +53,31 @@ int gvl_intervals_bucket_fill(const int32_t *itv_starts, const int32_t *itv_pmax
 
 // paint launches; `todo` (n_queries * n_chunks bytes, nullable) selects the tiled kernel + the per-value
 // kernel for the chunks it leaves, NULL the per-value kernel alone
-static bool paint_can_tile(const int32_t *pmax, int64_t max_row_len);
+static bool paint_can_tile(const int32_t *pmax, int64_t max_row_len) {
+    return pmax && max_row_len < 0x7FFFFF00ll && (max_row_len + 2047) / 2048 <= 0x7FFFFFFFll / 4;
+}
+// an interval set's coarse bucket index, when it has one and DBG_NO_BUCKET_INDEX does not take it away
+static PaintIndex paint_index(const gvl_track_set &T, int dbg) {
+    if (!T.bkt_offsets || !T.bkt_base || !T.bkt_lo || !T.bkt_hi || (dbg & DBG_NO_BUCKET_INDEX)) return PaintIndex{nullptr, nullptr, nullptr, nullptr};
+    return PaintIndex{(const i64 *)T.bkt_offsets, T.bkt_base, T.bkt_lo, T.bkt_hi};
+}
 static int paint_launch(const int64_t *offset_idxs, const int32_t *starts, int64_t starts_stride, int64_t n_queries,
                         const int32_t *itv_starts, const int32_t *itv_ends, const float *itv_values,
                         const int64_t *itv_offsets, const int32_t *itv_pmax_ends, float *out, const int64_t *out_offsets,
-                        int64_t max_row_len, PaintTodo *todo, hipStream_t s, const PaintIndex X = PaintIndex{nullptr, nullptr, nullptr, nullptr},
+                        int64_t max_row_len, PaintTodo *todo, hipStream_t s, int dbg, const PaintIndex X = PaintIndex{nullptr, nullptr, nullptr, nullptr},
                         bool tile_complete = false, i64 list_div = 1) {
     if (list_div < 1) list_div = 1;
     const int chunk_len = 2048;
     const i64 n_chunks = (max_row_len + chunk_len - 1) / chunk_len;
-    const bool complete_no_flags = !todo && tile_complete && X.offsets && !(debug_flags() & (8192 | 1024)) && paint_can_tile(itv_pmax_ends, max_row_len);
-    if (todo || complete_no_flags) {
-        // tile_complete: the interval set's owner vouches that the tiled kernel finishes every chunk (no overlaps, no equal
-        // starts, at most 256 candidates in any two adjacent index buckets), so the leftovers launch -- 5.8 us that find
-        // nothing -- is skipped; a chunk that needs it after all is reported through gvl_async_error, never silently wrong
-        const bool complete = tile_complete && X.offsets && !(debug_flags() & (8192 | 1024));
+    // tile_complete: the interval set's owner vouches that the tiled kernel finishes every chunk (no overlaps, no equal
+    // starts, at most 256 candidates in any two adjacent index buckets), so the leftovers launch -- 5.8 us that find
+    // nothing -- is skipped; a chunk that needs it after all is reported through gvl_async_error, never silently wrong
+    const bool complete = tile_complete && X.offsets && !(dbg & (DBG_PAINT_LDS_IMAGE | DBG_NO_BUCKET_INDEX));
+    if (todo || (complete && paint_can_tile(itv_pmax_ends, max_row_len))) {
         intervals_to_tracks_tiled_kernel<<<dim3((unsigned)((n_chunks + 3) / 4), (unsigned)n_queries), dim3(256), 0, s>>>(
             (const i64 *)offset_idxs, starts, (i64)starts_stride, (i64)n_queries, itv_starts, itv_ends, itv_values,
             (const i64 *)itv_offsets, itv_pmax_ends, out, (const i64 *)out_offsets, chunk_len, (int)n_chunks, todo, X,
-            (debug_flags() & 8192) ? 1 : 0, complete ? async_err_word() : nullptr, list_div);
+            (dbg & DBG_PAINT_LDS_IMAGE) ? 1 : 0, complete ? async_err_word() : nullptr, list_div);
         if (complete) return check_launch("gvl_intervals_to_tracks");
         intervals_to_tracks_kernel<<<dim3((unsigned)((n_chunks * n_queries + 255) / 256)), dim3(256), 0, s>>>(
             (const i64 *)offset_idxs, starts, (i64)starts_stride, (i64)n_queries, itv_starts, itv_ends, itv_values,
@@ -84,9 +90,6 @@ static int paint_launch(const int64_t *offset_idxs, const int32_t *starts, int64
             (const i64 *)itv_offsets, itv_pmax_ends, out, (const i64 *)out_offsets, chunk_len, nullptr, (i64)0, list_div);
     }
     return check_launch("gvl_intervals_to_tracks");
-}
-static bool paint_can_tile(const int32_t *pmax, int64_t max_row_len) {
-    return pmax && max_row_len < 0x7FFFFF00ll && (max_row_len + 2047) / 2048 <= 0x7FFFFFFFll / 4;
 }
 
 int gvl_intervals_to_tracks(const int64_t *offset_idxs, const int32_t *starts, int64_t starts_stride,
@@ -125,7 +128,7 @@ int gvl_intervals_to_tracks(const int64_t *offset_idxs, const int32_t *starts, i
         todo = nullptr;
     }
     const int rc = paint_launch(offset_idxs, starts, starts_stride, n_queries, itv_starts, itv_ends, itv_values, itv_offsets,
-                                itv_pmax_ends, out, out_offsets, max_row_len, todo, s);
+                                itv_pmax_ends, out, out_offsets, max_row_len, todo, s, debug_flags());
     if (todo) (void)hipFreeAsync(todo, s);
     if (scratch) (void)hipFreeAsync(scratch, s);
     return rc;
@@ -147,21 +150,20 @@ int gvl_paint_tracks(const gvl_track_set *ts, const int64_t *offset_idxs, const 
         return gvl_intervals_to_tracks(offset_idxs, starts, starts_stride, n_queries, ts->itv_starts, ts->itv_ends, ts->itv_values,
                                        ts->itv_offsets, ts->n_intervals, nullptr, out, out_offsets, max_row_len, stream);
     hipStream_t s = (hipStream_t)stream;
-    PaintIndex X{nullptr, nullptr, nullptr, nullptr};
-    if (ts->bkt_offsets && ts->bkt_base && ts->bkt_lo && ts->bkt_hi && !(debug_flags() & 1024))
-        X = PaintIndex{(const i64 *)ts->bkt_offsets, ts->bkt_base, ts->bkt_lo, ts->bkt_hi};
+    const int dbg = debug_flags();
+    const PaintIndex X = paint_index(*ts, dbg);
     const i64 n_chunks = (max_row_len + 2047) / 2048;
     PaintTodo *todo = nullptr;
     // (a tile_complete set with its index needs no flags and no second launch: no scratch allocation either -- the stream-ordered
     // malloc + free pair cost more than the painting itself)
-    const bool complete = ts->tile_complete != 0 && X.offsets && !(debug_flags() & (8192 | 1024));
+    const bool complete = ts->tile_complete != 0 && X.offsets && !(dbg & (DBG_PAINT_LDS_IMAGE | DBG_NO_BUCKET_INDEX));
     if (!complete && paint_can_tile(ts->itv_pmax_ends, max_row_len) &&
         pool_alloc((void **)&todo, (size_t)(n_queries * n_chunks) * sizeof(PaintTodo), s) != hipSuccess) {
         (void)hipGetLastError();
         todo = nullptr;
     }
     const int rc = paint_launch(offset_idxs, starts, starts_stride, n_queries, ts->itv_starts, ts->itv_ends, ts->itv_values,
-                                ts->itv_offsets, ts->itv_pmax_ends, out, out_offsets, max_row_len, todo, s, X,
+                                ts->itv_offsets, ts->itv_pmax_ends, out, out_offsets, max_row_len, todo, s, dbg, X,
                                 ts->tile_complete != 0, ts->list_div);
     if (todo) (void)hipFreeAsync(todo, s);
     return rc;
@@ -169,17 +171,8 @@ int gvl_paint_tracks(const gvl_track_set *ts, const int64_t *offset_idxs, const 
 
 static int realign_tracks_impl(const gvl_static *st, const gvl_batch *bt, const float *tracks,
                                const int64_t *track_offsets, const double *params, int64_t strategy_id,
-                               uint64_t base_seed, const u64 *seed_ptr, float *out, void *stream, const PaintSrcArgs *ps = nullptr,
-                               int2 *plan_hdr = nullptr, i32x4 *plan_ent = nullptr, bool plan_make = false, int to_shift = 0);
-int gvl_realign_tracks(const gvl_static *st, const gvl_batch *bt, const float *tracks,
-                       const int64_t *track_offsets, const double *params, int64_t strategy_id,
-                       uint64_t base_seed, float *out, void *stream) {
-    return realign_tracks_impl(st, bt, tracks, track_offsets, params, strategy_id, base_seed, nullptr, out, stream);
-}
-static int realign_tracks_impl(const gvl_static *st, const gvl_batch *bt, const float *tracks,
-                               const int64_t *track_offsets, const double *params, int64_t strategy_id,
-                               uint64_t base_seed, const u64 *seed_ptr, float *out, void *stream, const PaintSrcArgs *ps,
-                               int2 *plan_hdr, i32x4 *plan_ent, bool plan_make, int to_shift) {
+                               uint64_t base_seed, const u64 *seed_ptr, float *out, void *stream, int dbg, const PaintSrcArgs *ps = nullptr,
+                               int2 *plan_hdr = nullptr, i32x4 *plan_ent = nullptr, bool plan_make = false, int to_shift = 0) {
     if (!st || !bt) return fail(GVL_ERR_INVALID, "%s", "gvl_realign_tracks: NULL struct");
     if (bt->batch < 0 || bt->ploidy <= 0) return fail(GVL_ERR_INVALID, "%s", "gvl_realign_tracks: bad batch/ploidy");
     if (bt->batch == 0) return GVL_OK;
@@ -194,7 +187,7 @@ static int realign_tracks_impl(const gvl_static *st, const gvl_batch *bt, const 
     memset(&A, 0, sizeof(A));
     A.go_starts = (const i64 *)st->geno_o_starts; A.go_stops = (const i64 *)st->geno_o_stops;
     A.geno_v_idxs = st->geno_v_idxs; A.v_starts = st->v_starts; A.ilens = st->ilens; A.n_variants = st->n_variants;
-    A.grec = (debug_flags() & 16) ? nullptr : st->geno_rec;
+    A.grec = (dbg & DBG_NO_GENO_REC) ? nullptr : st->geno_rec;
     A.regions = bt->regions; A.regions_stride = bt->regions_stride; A.shifts = bt->shifts;
     A.geno_offset_idx = (const i64 *)bt->geno_offset_idx; A.keep = bt->keep; A.keep_offsets = (const i64 *)bt->keep_offsets;
     A.to_rc = bt->to_rc; A.out_offsets = (const i64 *)bt->out_offsets;
@@ -204,7 +197,7 @@ static int realign_tracks_impl(const gvl_static *st, const gvl_batch *bt, const 
     A.tracks = tracks; A.track_offsets = (const i64 *)track_offsets;
     A.param = params[0]; A.strategy = strategy_id; A.base_seed = base_seed; A.seed_ptr = seed_ptr;
     A.out = out;
-    A.dbg = debug_flags();
+    A.dbg = dbg;
     A.stamps = g_stamps;
     A.query_seed = (const i64 *)bt->query_seed;
     A.to_shift = to_shift;
@@ -213,7 +206,7 @@ static int realign_tracks_impl(const gvl_static *st, const gvl_batch *bt, const 
     // rows of several chunks: the rows' plans, once per batch (the caller's scratch; every track of the batch reads the same
     // ones -- the walk does not depend on the track): headers (int2 per (row, chunk)), then the entry tables
     // (int2 per (row, chunk) + PLAN_MAXE entries per row: the caller has made sure both fit)
-    if (plan_hdr && plan_ent && chunks > 1 && !(A.dbg & (8 | 268435456))) {
+    if (plan_hdr && plan_ent && chunks > 1 && !(A.dbg & (DBG_SCALAR_WALK | DBG_NO_TRACK_PLANS))) {
         if (plan_make) {
             track_plan_kernel<<<dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream>>>(A, plan_hdr, plan_ent, chunks, -1, 0);
             const int rc = check_launch("gvl_realign_tracks(row plans)");
@@ -222,12 +215,17 @@ static int realign_tracks_impl(const gvl_static *st, const gvl_batch *bt, const 
         A.plan_hdr = plan_hdr; A.plan_ent = plan_ent;
     }
     // tracks straight from the intervals with the rows' plans at hand: the fast kernel (chunks it does not take call the general body;
-    // GVL_DBG & 1073741824: the general kernel for every chunk, as in round 4)
-    if (ps && A.plan_hdr && A.plan_ent && A.out_offsets && !(A.dbg & (1073741824 | GVL_ABL(8388608) | GVL_ABL(16777216) | 2097152)))
+    // DBG_ROUND4_ROUTES: the general kernel for every chunk, as in round 4)
+    if (ps && A.plan_hdr && A.plan_ent && A.out_offsets && !(A.dbg & (DBG_ROUND4_ROUTES | GVL_ABL(DBG_ABL_TRACK_WALK) | GVL_ABL(DBG_ABL_TRACK_WINDOW) | DBG_NO_REALIGN_WINDOW)))
         realign_paint_kernel<<<dim3((unsigned)grid, (unsigned)chunks), dim3(256), 0, (hipStream_t)stream>>>(A, *ps);
     else if (ps) realign_tracks_kernel<true><<<dim3((unsigned)grid, (unsigned)chunks), dim3(256), 0, (hipStream_t)stream>>>(A, *ps);
     else realign_tracks_kernel<false><<<dim3((unsigned)grid, (unsigned)chunks), dim3(256), 0, (hipStream_t)stream>>>(A, PaintSrcArgs());
     return check_launch("gvl_realign_tracks");
+}
+int gvl_realign_tracks(const gvl_static *st, const gvl_batch *bt, const float *tracks,
+                       const int64_t *track_offsets, const double *params, int64_t strategy_id,
+                       uint64_t base_seed, float *out, void *stream) {
+    return realign_tracks_impl(st, bt, tracks, track_offsets, params, strategy_id, base_seed, nullptr, out, stream, debug_flags());
 }
 
 
@@ -299,10 +297,11 @@ int gvli::tracks_batch_impl(const gvl_static *st, const gvl_batch *bt, const int
     D.keep = nullptr; D.keep_offsets = nullptr;
     // (every track realigned straight from its intervals: nobody reads a scratch track, so only the LENGTHS are needed -- stored as
     // (0, length) pairs, no scan launch)
-    bool all_fused = !(debug_flags() & 4194304);
+    const int dbg = debug_flags();
+    bool all_fused = !(dbg & DBG_NO_FUSED_TRACKS);
     for (int t = 0; t < n_tracks && all_fused; ++t) {
         const gvl_track_set &T = tracks[t];
-        all_fused = T.tile_complete != 0 && T.bkt_offsets && T.bkt_base && T.bkt_lo && T.bkt_hi && !(debug_flags() & 1024) && T.itv_pmax_ends;
+        all_fused = T.tile_complete != 0 && paint_index(T, dbg).offsets && T.itv_pmax_ends;
     }
     int to_shift = 0;
     if (pre_track_offsets && pre_out_offsets) {
@@ -331,32 +330,30 @@ int gvli::tracks_batch_impl(const gvl_static *st, const gvl_batch *bt, const int
         const gvl_track_set &T = tracks[t];
         if (!T.itv_offsets || (T.n_intervals > 0 && (!T.itv_starts || !T.itv_ends || !T.itv_values)))
             return fail(GVL_ERR_INVALID, "%s", "gvl_tracks_batch: NULL interval array");
-        PaintIndex X{nullptr, nullptr, nullptr, nullptr};
-        if (T.bkt_offsets && T.bkt_base && T.bkt_lo && T.bkt_hi && !(debug_flags() & 1024))
-            X = PaintIndex{(const i64 *)T.bkt_offsets, T.bkt_base, T.bkt_lo, T.bkt_hi};
+        const PaintIndex X = paint_index(T, dbg);
         // the track's own insertion fill (_reconstruct.py:204-208 lowers one per track) or the call's
         const double t_par[1] = {T.has_fill ? T.fill_param : params[0]};
         const int64_t t_strategy = T.has_fill ? (int64_t)T.fill_strategy : strategy_id;
         // An interval set whose owner vouches for non-overlapping intervals (tile_complete) and that has its bucket
         // index is realigned straight from the intervals: the scratch track is neither written nor read (SrcPainted;
         // a window the claim does not hold for falls back to exact per-position lookups, it is never wrong).
-        const bool fused = T.tile_complete != 0 && X.offsets && T.itv_pmax_ends && !(debug_flags() & 4194304);
+        const bool fused = T.tile_complete != 0 && X.offsets && T.itv_pmax_ends && !(dbg & DBG_NO_FUSED_TRACKS);
         if (fused) {
             PaintSrcArgs ps{(const i64 *)offset_idxs, T.list_div > 1 ? T.list_div : 1, T.itv_starts, T.itv_ends, T.itv_values,
                             (const i64 *)T.itv_offsets, T.itv_pmax_ends, X};
             rc = realign_tracks_impl(st, &rb, nullptr, (const int64_t *)track_offsets, T.has_fill ? t_par : params, t_strategy, base_seed,
-                                     seed_ptr, out + (i64)t * out_track_stride, stream, &ps, plan_hdr, plan_ent, !plan_made, to_shift);
+                                     seed_ptr, out + (i64)t * out_track_stride, stream, dbg, &ps, plan_hdr, plan_ent, !plan_made, to_shift);
             if (rc) return rc;
             plan_made = true;
             continue;
         }
         rc = paint_launch(offset_idxs, bt->regions + 1, bt->regions_stride, B, T.itv_starts, T.itv_ends, T.itv_values, T.itv_offsets,
                           T.itv_pmax_ends, scr, (const int64_t *)track_offsets, scratch_stride,
-                          paint_can_tile(T.itv_pmax_ends, scratch_stride) ? todo : nullptr, s, X, T.tile_complete != 0,
+                          paint_can_tile(T.itv_pmax_ends, scratch_stride) ? todo : nullptr, s, dbg, X, T.tile_complete != 0,
                           T.list_div > 1 ? T.list_div : 1);
         if (rc) return rc;
         rc = realign_tracks_impl(st, &rb, scr, (const int64_t *)track_offsets, T.has_fill ? t_par : params, t_strategy, base_seed, seed_ptr,
-                                 out + (i64)t * out_track_stride, stream, nullptr, plan_hdr, plan_ent, !plan_made);
+                                 out + (i64)t * out_track_stride, stream, dbg, nullptr, plan_hdr, plan_ent, !plan_made);
         if (rc) return rc;
         plan_made = true;
     }

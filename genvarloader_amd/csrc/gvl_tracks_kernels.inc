@@ -402,7 +402,7 @@ __device__ __forceinline__ void realign_body(const TrackArgs &A, const PaintSrcA
     }
     // The row was planned as a whole (track_plan_kernel: by the native loop with its epoch table, or once per gvl_tracks_batch
     // call): the chunk's entries are `ph_count` consecutive ones of the row's table -- one read, no walk.
-    if (!walk_done && ph_count > 0 && ph_count <= SEG_CAP && !(A.dbg & (8 | 268435456))) {
+    if (!walk_done && ph_count > 0 && ph_count <= SEG_CAP && !(A.dbg & (DBG_SCALAR_WALK | DBG_NO_TRACK_PLANS))) {
         if (lane < ph_count) {
             const i32x4 e = A.plan_ent[k * (i64)PLAN_MAXE + ph_first + lane];
             M.out[lane] = e.x; M.kind[lane] = (e.y == T_FILL && A.strategy == GVL_FILL_REPEAT_5P) ? (int)T_REPEAT : e.y;
@@ -419,7 +419,7 @@ __device__ __forceinline__ void realign_body(const TrackArgs &A, const PaintSrcA
     // part in the shift (:312-314), every applied indel ends a track run, no lead pad.  It
     // writes the chunk's entries straight into the LDS table; anything it cannot express in
     // i32 / 64 entries leaves the table empty for the scalar walk below.
-    if (!walk_done && !(A.dbg & 8)) {
+    if (!walk_done && !(A.dbg & DBG_SCALAR_WALK)) {
         bool ok = q_start > -(1ll << 30) && q_start < (1ll << 30) && shift >= 0 && shift < (1ll << 30);
         int rem = (int)(ok ? shift : 0);
         int tidx0 = 0, pm_carry = 0, x_carry = 0;
@@ -595,7 +595,7 @@ __device__ __forceinline__ void realign_body(const TrackArgs &A, const PaintSrcA
             const PaintSrcArgs *const PS = &PS_;
 #endif
             i64 x_lo = 0; int wlen = 0;
-            if (paint_build_window(Wn_, PS, S.idx, q_start, tlen, x_first, lane, x_lo, wlen)) { S.x_lo = x_lo; S.wlen = wlen; S.win_ok = !(A.dbg & 2097152); }
+            if (paint_build_window(Wn_, PS, S.idx, q_start, tlen, x_first, lane, x_lo, wlen)) { S.x_lo = x_lo; S.wlen = wlen; S.win_ok = !(A.dbg & DBG_NO_REALIGN_WINDOW); }
         }
     };
 
@@ -681,7 +681,7 @@ __device__ __forceinline__ void realign_body(const TrackArgs &A, const PaintSrcA
 
         const int cov = out_idx < lo_clip ? lo_clip : (out_idx > hi_clip ? hi_clip : out_idx);
         const int limit = walk_done ? hi_clip : (cov & ~3);
-        if (A.dbg & GVL_ABL(8388608)) return;              // (timing ablation: head + walk only)
+        if (A.dbg & GVL_ABL(DBG_ABL_TRACK_WALK)) return;              // (timing ablation: head + walk only)
         if (PAINT && !have_win && nseg > 0) {
             // the first entry that reaches into the chunk says where its first value comes from
             // (entry 0: the table only holds entries that reach into what is still to be emitted)
@@ -700,7 +700,7 @@ __device__ __forceinline__ void realign_body(const TrackArgs &A, const PaintSrcA
         const int e_out = ev ? M.out[lane] : 0x7FFFFFFF, e_plo = ev ? M.plo[lane] : 0;
         const int e_kind = ev ? (M.kind[lane] | (M.phi[lane] == (e_plo >> 31) ? 0 : 256)) : T_ZERO;
         const bool tl32 = tlen < 0x7FFFFF00ll;
-        if (A.dbg & GVL_ABL(16777216)) return;             // (timing ablation: ... + the window)
+        if (A.dbg & GVL_ABL(DBG_ABL_TRACK_WINDOW)) return;             // (timing ablation: ... + the window)
         if (A.stamps && lane == 0) {
             if (PAINT && !S_win_ok(S)) atomicAdd((unsigned long long *)&A.stamps[10], 1ull);     // ... without a window
             if (nseg > 4) atomicAdd((unsigned long long *)&A.stamps[11], 1ull);                   // ... with more than 4 entries
@@ -868,7 +868,7 @@ __device__ __noinline__ void realign_chunk_general(const u64 kernarg, const Trac
 #endif
 }
 
-// (diagnostic builds with gvl_diag_set_stamps and GVL_DBG & 4096: a timeline -- 8 u64 per (row, chunk) behind the 64 counters, s_memrealtime
+// (diagnostic builds with gvl_diag_set_stamps and DBG_PAINT_TIMELINE: a timeline -- 8 u64 per (row, chunk) behind the 64 counters, s_memrealtime
 // (100 MHz) at the wave's start [0], window built [3], stores issued [5]: tools/stamps_paint.py.  Three stamps only: each is a scalar
 // memory operation, and a wait behind it serialises the head's rounds of scalar loads; the counters' same-address atomics are off then)
 #ifdef GVL_DIAG
@@ -886,14 +886,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     const int chunk = blockIdx.y;
     const int n_chunks = gridDim.y;
 #ifdef GVL_DIAG
-    const bool tl_on = A.stamps != nullptr && (A.dbg & 4096) != 0;
+    const bool tl_on = A.stamps != nullptr && (A.dbg & DBG_PAINT_TIMELINE) != 0;
 #endif
     PAINT_STAMP(0);
     const u64 kernarg = (u64)__builtin_amdgcn_kernarg_segment_ptr();
     typedef const int __attribute__((address_space(4))) *KInt;
     typedef const i64 __attribute__((address_space(4))) *KI64;
     PaintWin &W = wins[wave];
-    bool fast = A.plan_hdr != nullptr && A.plan_ent != nullptr && !(A.dbg & (8 | 268435456 | 2097152)) && A.out_offsets != nullptr;
+    bool fast = A.plan_hdr != nullptr && A.plan_ent != nullptr && !(A.dbg & (DBG_SCALAR_WALK | DBG_NO_TRACK_PLANS | DBG_NO_REALIGN_WINDOW)) && A.out_offsets != nullptr;
     // ---- head: what the row's number alone addresses, one round of scalar loads (no shift, genotype slot or keep mask: the plan holds the walk)
     const i64 query = A.ploidy_shift >= 0 ? (k >> A.ploidy_shift) : (i64)((u32)k / (u32)A.ploidy);
     int ph_first = 0, ph_count = -1;
@@ -1085,7 +1085,7 @@ __global__ __launch_bounds__(256) void track_plan_kernel(const TrackArgs A, int2
     const i64 tq = tl_bs > 0 ? query + query / tl_bs : (query << A.to_shift);
     const i64 tlen = A.track_offsets[tq + 1] - A.track_offsets[tq];
     i32x4 *const ent = ent_all + k * (i64)PLAN_MAXE;
-    bool ok = q_start > -(1ll << 30) && q_start < (1ll << 30) && shift >= 0 && shift < (1ll << 30) && !(A.dbg & 8) && n_var > 0 &&
+    bool ok = q_start > -(1ll << 30) && q_start < (1ll << 30) && shift >= 0 && shift < (1ll << 30) && !(A.dbg & DBG_SCALAR_WALK) && n_var > 0 &&
               L64 > 0 && L64 < 0x7FFFFF00ll;
     int rem = (int)(ok ? shift : 0);
     int tidx0 = 0, pm_carry = 0, x_carry = 0;

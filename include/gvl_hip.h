@@ -184,7 +184,7 @@ typedef struct gvl_out {
 
 int gvl_abi_version(void);
 /* Test / diagnostic switches (the bits of the GVL_DBG environment variable, see
- * debug_flags() in gvl_hip.hip); flags < 0 returns to the environment's value. */
+ * enum DbgBit in csrc/gvl_internal.inc); flags < 0 returns to the environment's value. */
 int gvl_set_debug_flags(int flags);
 /* Launch-policy overrides, process-wide: for A/B measurements and for tests that must force a schedule the built-in policy
  * would not pick at their sizes.  value <= 0 returns the key to the built-in policy.  Results never depend on them.
