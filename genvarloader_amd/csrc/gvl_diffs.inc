@@ -215,17 +215,33 @@ __global__ __launch_bounds__(1024) void offsets_scan_kernel(i64 *offs, i64 n, i6
 // Scratch-track lengths of a haps + tracks batch (_reconstruct.py:191): per query,
 // len - min over haplotypes of min(diff, 0) with diff = the haplotype's length delta inside the
 // window (query mode of get_diffs_sparse); written at lengths[q + 1] for the scan.  Also the
-// (batch * ploidy + 1) fixed-length output offsets k * L that the realign kernel reads.
+// (batch * ploidy + 1) fixed-length output offsets k * L that the realign kernel reads (ROW_OFFS).  Ragged rows (!ROW_OFFS): the
+// caller's offsets (caller_offsets, never written) clamped to [0, batch * ploidy * len_cap] into out_offsets, which the realignment then
+// reads -- nothing lands past a track's capacity -- and a row longer than A.len_cap or outside that capacity is reported through
+// A.async_err.
 // `pairs` != 0: lengths as (0, length) PAIRS per query -- what the realignment straight from the intervals needs (only differences of
 // the offsets are read there: no scratch track, so no prefix sum and no scan launch).
 // Ploidy 1 / 2 / 4 (round 6): a wave per (query, HAPLOTYPE) -- the haplotypes of a query share a workgroup and meet in LDS -- instead
 // of one wave walking the query's haplotypes one after the other (12 us of a stand-alone gvl_tracks_batch for 128 queries of 170
 // variants per haplotype).
+template <bool ROW_OFFS>
 __global__ __launch_bounds__(256) void track_lengths_kernel(const DiffArgs A, const int *regions, i64 regions_stride, i64 batch,
-                                                             i64 out_len, i64 *lengths, i64 *out_offsets, int pairs) {
+                                                             i64 out_len, i64 *lengths, i64 *out_offsets, int pairs, const i64 *caller_offsets) {
     const i64 t = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     const i64 K = batch * A.ploidy;
-    for (i64 k = t; k <= K; k += (i64)gridDim.x * blockDim.x) out_offsets[k] = k * out_len;
+    if constexpr (ROW_OFFS) {
+        for (i64 k = t; k <= K; k += (i64)gridDim.x * blockDim.x) out_offsets[k] = k * out_len;
+    } else {
+        const i64 cap = K * A.len_cap;
+        for (i64 k = t; k <= K; k += (i64)gridDim.x * blockDim.x) {
+            const i64 o0 = caller_offsets[k];
+            out_offsets[k] = o0 < 0 ? 0 : (o0 > cap ? cap : o0);
+            if (k < K) {
+                const i64 o1 = caller_offsets[k + 1];
+                if ((o0 < 0 || o1 < o0 || o1 - o0 > A.len_cap || o1 > cap) && A.async_err) atomicOr(A.async_err, 1);
+            }
+        }
+    }
     const int lane = threadIdx.x & (WAVE - 1);
     auto put = [&](const i64 q, const i64 len) {
         if (pairs) { lengths[2 * q] = 0; lengths[2 * q + 1] = len; }
@@ -266,11 +282,13 @@ __global__ __launch_bounds__(256) void track_lengths_kernel(const DiffArgs A, co
 // every query are known there), laid out per batch: batch j's (bs + 1) scan slots at lengths[j * (bs + 1) ..],
 // slot 0 = 0; track_scan_batches_kernel then turns each batch's slots into its scratch-track offsets.  A batch
 // of the epoch then costs no sizing launch at all (they were 19 us of cfg4's 143 us step).
+template <bool ROW_OFFS>
 __global__ __launch_bounds__(256) void track_lengths_epoch_kernel(const DiffArgs A, const int *regions, i64 regions_stride, i64 n,
                                                                    i64 bs, i64 out_len, i64 *lengths, i64 *out_offsets) {
     const i64 t = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     const i64 K = bs * A.ploidy;
-    for (i64 k = t; k <= K; k += (i64)gridDim.x * blockDim.x) out_offsets[k] = k * out_len;
+    if constexpr (ROW_OFFS)
+        for (i64 k = t; k <= K; k += (i64)gridDim.x * blockDim.x) out_offsets[k] = k * out_len;
     const int lane = threadIdx.x & (WAVE - 1);
     const i64 q = t >> 6;                                    // one wave per query
     if (q >= n) return;

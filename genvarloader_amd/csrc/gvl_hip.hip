@@ -341,11 +341,12 @@ int pick_chunk(i64 max_len, int *chunks, int *chunk_len) {
 // GVL_DBG (read once; gvl_set_debug_flags overrides it): the bits are DbgBit, gvl_internal.inc.  Each C-ABI entry point reads it
 // once and passes the value down (ReconArgs::dbg, TrackArgs::dbg); the native loop snapshots it per epoch table (LoaderKnobs).
 // (written by gvl_set_debug_flags on one thread while the loader's producer thread reads it: a relaxed atomic)
+// (-1: the environment's value.  The bits fill all 32: DBG_CHUNK_LIST is the sign bit, GVL_DBG=2147483648 sets it)
 int g_debug_override = -1;
 int debug_flags() {
-    static const int flags = [] { const char *e = getenv("GVL_DBG"); return e ? atoi(e) : 0; }();
+    static const int flags = [] { const char *e = getenv("GVL_DBG"); return e ? (int)(u32)strtoll(e, nullptr, 10) : 0; }();
     const int ov = __atomic_load_n(&g_debug_override, __ATOMIC_RELAXED);
-    const int v = ov >= 0 ? ov : flags;
+    const int v = ov != -1 ? ov : flags;
 #ifdef GVL_DIAG
     return v;
 #else
@@ -1245,10 +1246,12 @@ static LoaderKnobs loader_knobs_now() {
     k.dbg = debug_flags() & DBG_LOADER_KNOBS;
     return k;
 }
+static i64 loader_row_cap(const gvl_loader_config *c);
 static i64 loader_track_plan_bytes(const gvl_loader_config *cfg, i64 n, const LoaderKnobs &kn) {
-    if (cfg->output_length <= 2048) return 0;
+    const i64 L = loader_row_cap(cfg);          // (ragged rows: their bound)
+    if (L <= 2048) return 0;
     int chunks = 1, chunk_len = 0;
-    if (pick_chunk(cfg->output_length, &chunks, &chunk_len) || chunks <= 1) return 0;
+    if (pick_chunk(L, &chunks, &chunk_len) || chunks <= 1) return 0;
     const i64 cap_t = kn.track_cap_mb;
     const i64 cap = (cap_t > 0 ? cap_t : 512) << 20;
     const i64 b = track_plan_bytes(n * cfg->ploidy, chunks);
@@ -1332,10 +1335,10 @@ int gvl_loader_create(const gvl_static *st, const gvl_loader_config *cfg, gvl_lo
         cfg->ploidy <= 0 || (cfg->output_length <= 0 && cfg->output_length != -1) ||
         (!cfg->want_haps && !cfg->want_onehot && !cfg->want_annot))
         return fail(GVL_ERR_INVALID, "%s", "gvl_loader_create: bad config");
-    if (loader_ragged(cfg) && (cfg->max_row_len <= 0 || cfg->max_row_len > 0x7FFFFF00ll || !cfg->deterministic || cfg->n_tracks > 0 ||
-                               (cfg->want_onehot && cfg->onehot_layout != GVL_ONEHOT_LC)))
+    if (loader_ragged(cfg) && (cfg->max_row_len <= 0 || cfg->max_row_len > 0x7FFFFF00ll || !cfg->deterministic ||
+                               (cfg->want_onehot && cfg->onehot_layout != GVL_ONEHOT_LC) || (cfg->n_tracks > 0 && cfg->want_annot)))
         return fail(GVL_ERR_INVALID, "%s", "gvl_loader_create: ragged rows (output_length -1) need max_row_len > 0, deterministic != 0, "
-                                           "row-major one-hot and no tracks");
+                                           "row-major one-hot and, with tracks, no annotations");
     if (cfg->n_tracks < 0 || cfg->n_tracks > 16 || (cfg->n_tracks > 0 && (!cfg->tracks || cfg->scratch_stride <= 0 || cfg->batch_size > 65535 ||
                                                                           cfg->strategy_id < 0 || cfg->strategy_id > GVL_FILL_INTERPOLATE)))
         return fail(GVL_ERR_INVALID, "%s", "gvl_loader_create: tracks need 1..16 interval stores, scratch_stride > 0, batch_size <= 65535 "
@@ -1481,15 +1484,21 @@ static int loader_fill_table(gvl_loader *ld, const int64_t *order, i64 n, int32_
         D.keep = nullptr; D.keep_offsets = nullptr;
         const i64 grid = (n_used * WAVE + 255) / 256;
         if (grid > 0x7FFFFFFFll) return fail(GVL_ERR_UNSUPPORTED, "%s", "gvl_loader_start_epoch: too many queries for the track sizing");
-        track_lengths_epoch_kernel<<<dim3((unsigned)grid), dim3(256), 0, s>>>(D, t_regions, 4, n_used, bs, c.output_length,
-                                                                               t_track_offsets, t_out_offsets);
+        // (ragged rows: the row offsets are the haplotypes', sized above or per group / batch; the k * L ones are not written)
+        if (loader_ragged(&c))
+            track_lengths_epoch_kernel<false><<<dim3((unsigned)grid), dim3(256), 0, s>>>(D, t_regions, 4, n_used, bs, 0, t_track_offsets, nullptr);
+        else
+            track_lengths_epoch_kernel<true><<<dim3((unsigned)grid), dim3(256), 0, s>>>(D, t_regions, 4, n_used, bs, c.output_length,
+                                                                                         t_track_offsets, t_out_offsets);
         rc3 = check_launch("gvl_loader_start_epoch(track lengths)");
         if (rc3) return rc3;
         track_scan_batches_kernel<<<dim3((unsigned)n_batches), dim3(256), 0, s>>>(t_track_offsets, n_used, bs);
         rc3 = check_launch("gvl_loader_start_epoch(track offsets)");
         if (rc3) return rc3;
-        // rows of several chunks: the rows' plans (track_plan_kernel), for every row of the epoch
-        if (po[8] > po[7] && !(kn.dbg & (DBG_SCALAR_WALK | DBG_NO_TRACK_PLANS))) {
+        // rows of several chunks: the rows' plans (track_plan_kernel), for every row of the epoch (ragged rows: when the epoch's row
+        // offsets are in the table; sized per group or batch, the batch's call plans its rows itself)
+        const bool rag_rows = loader_ragged(&c);
+        if (po[8] > po[7] && !(kn.dbg & (DBG_SCALAR_WALK | DBG_NO_TRACK_PLANS)) && (!rag_rows || loader_epoch_sizing(&ld->st, &c, kn))) {
             TrackArgs TA;
             memset(&TA, 0, sizeof(TA));
             TA.go_starts = (const i64 *)ld->st.geno_o_starts; TA.go_stops = (const i64 *)ld->st.geno_o_stops;
@@ -1498,14 +1507,15 @@ static int loader_fill_table(gvl_loader *ld, const int64_t *order, i64 n, int32_
             TA.regions = t_regions; TA.regions_stride = 4; TA.shifts = t_shifts; TA.geno_offset_idx = t_goi;
             TA.n_rows = n_used * c.ploidy; TA.ploidy = (int)c.ploidy; TA.ploidy_shift = log2_exact(c.ploidy);
             int chunks = 1;
-            if (pick_chunk(c.output_length, &chunks, &TA.chunk_len)) return fail(GVL_ERR_INVALID, "%s", "gvl_loader_start_epoch: too many chunks");
+            if (pick_chunk(loader_row_cap(&c), &chunks, &TA.chunk_len)) return fail(GVL_ERR_INVALID, "%s", "gvl_loader_start_epoch: too many chunks");
             TA.dbg = debug_flags();
             const i64 wgrid = (TA.n_rows + 3) / 4;
             if (wgrid > 0x7FFFFFFFll) return fail(GVL_ERR_UNSUPPORTED, "%s", "gvl_loader_start_epoch: too many rows for the walk states");
             TA.track_offsets = t_track_offsets;
             int2 *const ph = (int2 *)(base + po[7]);
             i32x4 *const pe = (i32x4 *)(base + po[7] + align256(TA.n_rows * (i64)chunks * (i64)sizeof(int2)));
-            rc3 = launch_track_plan(TA, ph, pe, chunks, c.output_length, bs, s);
+            TA.out_offsets = rag_rows ? (const i64 *)(base + po[9]) : nullptr;     // (ragged: batch j's rows at (bs * P + 1) j ..)
+            rc3 = launch_track_plan(TA, ph, pe, chunks, rag_rows ? -1 : c.output_length, bs, s);
             if (rc3) return rc3;
         }
     }
@@ -1593,8 +1603,8 @@ int gvl_loader_start_epoch(gvl_loader *ld, const int64_t *order, int64_t n, int3
         const i64 wsb = c.n_tracks > 0 ? loader_track_plan_bytes(&c, n, kn) : 0;
         int cl = 0;
         ld->e_chunks = 1;
-        if (wsb > 0) (void)pick_chunk(c.output_length, &ld->e_chunks, &cl);
-        const bool planned = wsb > 0 && !(kn.dbg & (DBG_SCALAR_WALK | DBG_NO_TRACK_PLANS));
+        if (wsb > 0) (void)pick_chunk(loader_row_cap(&c), &ld->e_chunks, &cl);
+        const bool planned = wsb > 0 && !(kn.dbg & (DBG_SCALAR_WALK | DBG_NO_TRACK_PLANS)) && (!loader_ragged(&c) || ld->e_rag_offs);
         // (the table was filled for n_used = every query of a whole batch, or all n: the plan's two parts are laid out for that many rows)
         const i64 n_used_rows = (drop_last ? (n / c.batch_size) * c.batch_size : n) * c.ploidy;
         ld->e_plan_hdr = planned ? (int2 *)(base + po[7]) : nullptr;
@@ -1737,12 +1747,12 @@ static int loader_submit(gvl_loader *ld, i64 g) {
         for (i64 j = g * ld->G; j < (g + 1) * ld->G && j < ld->n_batches; ++j, ++m) {
             gvl_loader_batch o;
             loader_parts(ld, j, &o);
-            const i64 K = c.batch_size * c.ploidy;
+            const i64 K = c.batch_size * c.ploidy;      // (track t of every batch, a short last one too, at t * K * row capacity)
             const double par[1] = {c.track_param};
             u8 *base = (u8 *)ld->arenas[o.slot];
             (void)traced("launch tracks", [&] {
                 rc = tracks_batch_impl(&ld->st, &bts[m], (const int64_t *)o.idx, ld->tracks, c.n_tracks, par, c.strategy_id, c.track_seed,
-                                       (const u64 *)o.track_seed, o.tracks, K * c.output_length, base + ld->part[10], c.scratch_stride, s,
+                                       (const u64 *)o.track_seed, o.tracks, K * loader_row_cap(&c), base + ld->part[10], c.scratch_stride, s,
                                        (debug_flags() & DBG_TRACK_SIZING_PER_BATCH) ? nullptr : ld->e_track_offsets + j * (c.batch_size + 1),
                                        (debug_flags() & DBG_TRACK_SIZING_PER_BATCH) ? nullptr : ld->e_out_offsets,
                                        ld->e_plan_hdr ? ld->e_plan_hdr + j * c.batch_size * c.ploidy * (i64)ld->e_chunks : nullptr,

@@ -92,6 +92,8 @@ enum DbgBit : int {
     DBG_NO_HAP_PLANS     = 536870912,   // rows of several chunks go without chunk plans (hap_plan_kernel): every chunk-wave walks its row
     DBG_ROUND4_ROUTES    = 1073741824,  // round 4's routing of the other output modes: channel-major one-hot, keep masks, annotations,
                                         // get_reference and the fast track kernel run the all-purpose (general) kernel
+    DBG_CHUNK_LIST       = (int)0x80000000u,    // ragged track rows of several chunks through their chunk list (1-D launches) instead of the
+                                        // rows x chunks grid with early exit; gvl_set_debug_flags(INT_MIN | ...) or GVL_DBG=2147483648
 };
 // The [ablation] bits change the output: they exist in -DGVL_DIAG builds only (tools/ablate.sh builds one next to the shipped
 // library).  The shipped library masks them off on the host (debug_flags) and compiles their tests out of the kernels

@@ -172,7 +172,8 @@ int gvl_paint_tracks(const gvl_track_set *ts, const int64_t *offset_idxs, const 
 static int realign_tracks_impl(const gvl_static *st, const gvl_batch *bt, const float *tracks,
                                const int64_t *track_offsets, const double *params, int64_t strategy_id,
                                uint64_t base_seed, const u64 *seed_ptr, float *out, void *stream, int dbg, const PaintSrcArgs *ps = nullptr,
-                               int2 *plan_hdr = nullptr, i32x4 *plan_ent = nullptr, bool plan_make = false, int to_shift = 0) {
+                               int2 *plan_hdr = nullptr, i32x4 *plan_ent = nullptr, bool plan_make = false, int to_shift = 0,
+                               const int2 *list = nullptr, const int *list_count = nullptr) {
     if (!st || !bt) return fail(GVL_ERR_INVALID, "%s", "gvl_realign_tracks: NULL struct");
     if (bt->batch < 0 || bt->ploidy <= 0) return fail(GVL_ERR_INVALID, "%s", "gvl_realign_tracks: bad batch/ploidy");
     if (bt->batch == 0) return GVL_OK;
@@ -208,7 +209,7 @@ static int realign_tracks_impl(const gvl_static *st, const gvl_batch *bt, const 
     // (int2 per (row, chunk) + PLAN_MAXE entries per row: the caller has made sure both fit)
     if (plan_hdr && plan_ent && chunks > 1 && !(A.dbg & (DBG_SCALAR_WALK | DBG_NO_TRACK_PLANS))) {
         if (plan_make) {
-            track_plan_kernel<<<dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream>>>(A, plan_hdr, plan_ent, chunks, -1, 0);
+            track_plan_kernel<false><<<dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream>>>(A, plan_hdr, plan_ent, chunks, -1, 0);
             const int rc = check_launch("gvl_realign_tracks(row plans)");
             if (rc) return rc;
         }
@@ -216,7 +217,18 @@ static int realign_tracks_impl(const gvl_static *st, const gvl_batch *bt, const 
     }
     // tracks straight from the intervals with the rows' plans at hand: the fast kernel (chunks it does not take call the general body;
     // DBG_ROUND4_ROUTES: the general kernel for every chunk, as in round 4)
-    if (ps && A.plan_hdr && A.plan_ent && A.out_offsets && !(A.dbg & (DBG_ROUND4_ROUTES | GVL_ABL(DBG_ABL_TRACK_WALK) | GVL_ABL(DBG_ABL_TRACK_WINDOW) | DBG_NO_REALIGN_WINDOW)))
+    const bool paint_fast = ps && A.plan_hdr && A.plan_ent && A.out_offsets &&
+                            !(A.dbg & (DBG_ROUND4_ROUTES | GVL_ABL(DBG_ABL_TRACK_WALK) | GVL_ABL(DBG_ABL_TRACK_WINDOW) | DBG_NO_REALIGN_WINDOW));
+    if (list && list_count) {
+        // ragged rows with their chunk list (gvl_tracks_batch): the 1-D launches, a wave per listed (row, chunk)
+        i64 lgrid = (A.n_rows * chunks + 3) / 4;
+        if (lgrid > CHUNK_LIST_WGS) lgrid = CHUNK_LIST_WGS;
+        if (paint_fast) realign_paint_list_kernel<<<dim3((unsigned)lgrid), dim3(256), 0, (hipStream_t)stream>>>(A, *ps, list, list_count, chunks);
+        else if (ps) realign_tracks_list_kernel<true><<<dim3((unsigned)lgrid), dim3(256), 0, (hipStream_t)stream>>>(A, *ps, list, list_count, chunks);
+        else realign_tracks_list_kernel<false><<<dim3((unsigned)lgrid), dim3(256), 0, (hipStream_t)stream>>>(A, PaintSrcArgs(), list, list_count, chunks);
+        return check_launch("gvl_realign_tracks(chunk list)");
+    }
+    if (paint_fast)
         realign_paint_kernel<<<dim3((unsigned)grid, (unsigned)chunks), dim3(256), 0, (hipStream_t)stream>>>(A, *ps);
     else if (ps) realign_tracks_kernel<true><<<dim3((unsigned)grid, (unsigned)chunks), dim3(256), 0, (hipStream_t)stream>>>(A, *ps);
     else realign_tracks_kernel<false><<<dim3((unsigned)grid, (unsigned)chunks), dim3(256), 0, (hipStream_t)stream>>>(A, PaintSrcArgs());
@@ -229,8 +241,8 @@ int gvl_realign_tracks(const gvl_static *st, const gvl_batch *bt, const float *t
 }
 
 
-// scratch layout of gvl_tracks_batch: track_offsets i64 (batch + 1) | out_offsets i64 (batch * ploidy + 1) |
-// chunk records (16 B x batch * chunks) | scratch tracks f32 (batch * stride) | row plans (track_plan_bytes)
+// scratch layout of gvl_tracks_batch: track_offsets i64 (batch + 1) | out_offsets i64 (batch * ploidy + 1; ragged rows: the caller's,
+// clamped to the tracks' capacity) | chunk records (16 B x batch * chunks) | scratch tracks f32 (batch * stride) | row plans (track_plan_bytes)
 static void tracks_scratch_parts(i64 batch, i64 ploidy, i64 stride, i64 part[6]) {
     const i64 n_chunks = (stride + 2047) / 2048;
     const i64 sz[5] = {16 * (batch + 1), 8 * (batch * ploidy + 1), batch * n_chunks * (i64)sizeof(PaintTodo), 4 * batch * stride,
@@ -260,15 +272,20 @@ int gvli::tracks_batch_impl(const gvl_static *st, const gvl_batch *bt, const int
                              float *out, int64_t out_track_stride, void *scratch, int64_t scratch_stride, void *stream,
                              const i64 *pre_track_offsets, const i64 *pre_out_offsets, const int2 *pre_plan_hdr, const i32x4 *pre_plan_ent) {
     if (!st || !bt || n_tracks < 0) return fail(GVL_ERR_INVALID, "%s", "gvl_tracks_batch: bad arguments");
-    if (bt->batch < 0 || bt->ploidy <= 0 || bt->output_length < 0)
-        return fail(GVL_ERR_INVALID, "%s", "gvl_tracks_batch: needs batch >= 0, ploidy > 0 and a fixed output_length");
+    if (bt->batch < 0 || bt->ploidy <= 0 || (bt->output_length < 0 && (bt->output_length != -1 || !bt->out_offsets || bt->max_row_len <= 0)))
+        return fail(GVL_ERR_INVALID, "%s", "gvl_tracks_batch: needs batch >= 0, ploidy > 0 and a fixed output_length, or output_length -1 "
+                                           "with the rows' out_offsets and max_row_len > 0");
     if (bt->batch == 0 || n_tracks == 0) return GVL_OK;
     if (bt->batch > 65535) return fail(GVL_ERR_UNSUPPORTED, "%s", "gvl_tracks_batch: more than 65535 queries per call");
     if (!bt->regions || !bt->shifts || !bt->geno_offset_idx || bt->regions_stride < 3 || !offset_idxs || !tracks || !params ||
         !out || !scratch || ((uintptr_t)scratch & 255) || scratch_stride <= 0 || scratch_stride > 0x7FFFFF00ll)
         return fail(GVL_ERR_INVALID, "%s", "gvl_tracks_batch: NULL/invalid array (scratch: gvl_tracks_scratch_bytes(), 256-byte aligned)");
-    const i64 B = bt->batch, P = bt->ploidy, L = bt->output_length;
-    if (out_track_stride < B * P * L) return fail(GVL_ERR_INVALID, "%s", "gvl_tracks_batch: out_track_stride < batch * ploidy * output_length");
+    // ragged rows (output_length -1): track t's row k is out[t * out_track_stride + out_offsets[k] ..], the haplotypes' offsets
+    const bool ragged = bt->output_length < 0;
+    const i64 B = bt->batch, P = bt->ploidy, L = ragged ? bt->max_row_len : bt->output_length;
+    if (L > 0x7FFFFF00ll) return fail(GVL_ERR_INVALID, "%s", "gvl_tracks_batch: bad max_row_len");
+    if (out_track_stride < B * P * L)
+        return fail(GVL_ERR_INVALID, "%s", "gvl_tracks_batch: out_track_stride < batch * ploidy * output_length (ragged: max_row_len)");
     hipStream_t s = (hipStream_t)stream;
     i64 part[6];
     tracks_scratch_parts(B, P, scratch_stride, part);
@@ -304,21 +321,53 @@ int gvli::tracks_batch_impl(const gvl_static *st, const gvl_batch *bt, const int
         all_fused = T.tile_complete != 0 && paint_index(T, dbg).offsets && T.itv_pmax_ends;
     }
     int to_shift = 0;
-    if (pre_track_offsets && pre_out_offsets) {
+    if (pre_track_offsets && (pre_out_offsets || ragged)) {
         track_offsets = const_cast<i64 *>(pre_track_offsets);
-        out_offsets = const_cast<i64 *>(pre_out_offsets);
+        out_offsets = ragged ? const_cast<i64 *>((const i64 *)bt->out_offsets) : const_cast<i64 *>(pre_out_offsets);
     } else {
         const bool per_hap = P == 1 || P == 2 || P == 4;      // a wave per (query, haplotype), 4 / P queries per workgroup
         const i64 grid = per_hap ? (B * P + 3) / 4 : (B * WAVE + 255) / 256;
-        // (the kernel also writes the K + 1 row offsets, grid-stride: any grid covers them)
+        // (the fixed form also writes the K + 1 row offsets, grid-stride: any grid covers them; ragged rows come with the caller's)
         to_shift = all_fused ? 1 : 0;
-        track_lengths_kernel<<<dim3((unsigned)grid), dim3(256), 0, s>>>(D, bt->regions, (i64)bt->regions_stride, B, L, track_offsets, out_offsets, to_shift);
+        if (ragged) {
+            // (the caller's rows clamped to the tracks' capacity into the scratch's out_offsets; rows past the bound are reported)
+            D.len_cap = L; D.async_err = async_err_word();
+            track_lengths_kernel<false><<<dim3((unsigned)grid), dim3(256), 0, s>>>(D, bt->regions, (i64)bt->regions_stride, B, L, track_offsets,
+                                                                                  out_offsets, to_shift, (const i64 *)bt->out_offsets);
+        } else {
+            track_lengths_kernel<true><<<dim3((unsigned)grid), dim3(256), 0, s>>>(D, bt->regions, (i64)bt->regions_stride, B, L, track_offsets,
+                                                                                 out_offsets, to_shift, nullptr);
+        }
         rc = check_launch("gvl_tracks_batch(lengths)");
         if (rc) return rc;
         if (!all_fused) {
             offsets_scan_kernel<<<dim3(1), dim3(1024), 0, s>>>(track_offsets, B, (i64 *)nullptr);
             rc = check_launch("gvl_tracks_batch(scan)");
             if (rc) return rc;
+        }
+    }
+    // ragged rows of several chunks: the rows x chunks grid, whose chunk-waves past their row's end exit -- or (DBG_CHUNK_LIST) the
+    // (row, chunk) pairs that hold values, listed once per call, and the 1-D launches over them.  The list launches 8 192 waves instead
+    // of 40 960 for 4 096 rows of 200 - 20 000 bases but is slower, not 10 % faster (profiles/r07_ragged_tracks.jsonl):
+    // not the default
+    // (the list lives in stream-ordered memory of the library's pool, not in the caller's scratch: the default schedule needs none)
+    const int2 *list = nullptr;
+    const int *list_count = nullptr;
+    u8 *list_mem = nullptr;
+    if (ragged && (dbg & DBG_CHUNK_LIST)) {
+        int lc = 1, lcl = 0;
+        if (!pick_chunk(L, &lc, &lcl) && lc > 1) {
+            if (pool_alloc((void **)&list_mem, (size_t)(256 + B * P * (i64)lc * (i64)sizeof(int2)), s) != hipSuccess) {
+                (void)hipGetLastError();
+                list_mem = nullptr;          // (then the grid)
+            } else {
+                int *cnt = (int *)list_mem;
+                int2 *lst = (int2 *)(list_mem + 256);
+                track_chunk_list_kernel<<<dim3(1), dim3(1024), 0, s>>>(out_offsets, B * P, lcl, lc, L, B * P * L, lst, cnt, async_err_word());
+                rc = check_launch("gvl_tracks_batch(chunk list)");
+                if (rc) { (void)hipFreeAsync(list_mem, s); return rc; }
+                list = lst; list_count = cnt;
+            }
         }
     }
     // 2. per track: paint the query's intervals into its scratch track, realign it to every haplotype
@@ -328,8 +377,10 @@ int gvli::tracks_batch_impl(const gvl_static *st, const gvl_batch *bt, const int
     rb.output_length = -1;
     for (int t = 0; t < n_tracks; ++t) {
         const gvl_track_set &T = tracks[t];
-        if (!T.itv_offsets || (T.n_intervals > 0 && (!T.itv_starts || !T.itv_ends || !T.itv_values)))
-            return fail(GVL_ERR_INVALID, "%s", "gvl_tracks_batch: NULL interval array");
+        if (!T.itv_offsets || (T.n_intervals > 0 && (!T.itv_starts || !T.itv_ends || !T.itv_values))) {
+            rc = fail(GVL_ERR_INVALID, "%s", "gvl_tracks_batch: NULL interval array");
+            break;
+        }
         const PaintIndex X = paint_index(T, dbg);
         // the track's own insertion fill (_reconstruct.py:204-208 lowers one per track) or the call's
         const double t_par[1] = {T.has_fill ? T.fill_param : params[0]};
@@ -342,8 +393,9 @@ int gvli::tracks_batch_impl(const gvl_static *st, const gvl_batch *bt, const int
             PaintSrcArgs ps{(const i64 *)offset_idxs, T.list_div > 1 ? T.list_div : 1, T.itv_starts, T.itv_ends, T.itv_values,
                             (const i64 *)T.itv_offsets, T.itv_pmax_ends, X};
             rc = realign_tracks_impl(st, &rb, nullptr, (const int64_t *)track_offsets, T.has_fill ? t_par : params, t_strategy, base_seed,
-                                     seed_ptr, out + (i64)t * out_track_stride, stream, dbg, &ps, plan_hdr, plan_ent, !plan_made, to_shift);
-            if (rc) return rc;
+                                     seed_ptr, out + (i64)t * out_track_stride, stream, dbg, &ps, plan_hdr, plan_ent, !plan_made, to_shift,
+                                     list, list_count);
+            if (rc) break;
             plan_made = true;
             continue;
         }
@@ -351,18 +403,23 @@ int gvli::tracks_batch_impl(const gvl_static *st, const gvl_batch *bt, const int
                           T.itv_pmax_ends, scr, (const int64_t *)track_offsets, scratch_stride,
                           paint_can_tile(T.itv_pmax_ends, scratch_stride) ? todo : nullptr, s, dbg, X, T.tile_complete != 0,
                           T.list_div > 1 ? T.list_div : 1);
-        if (rc) return rc;
+        if (rc) break;
         rc = realign_tracks_impl(st, &rb, scr, (const int64_t *)track_offsets, T.has_fill ? t_par : params, t_strategy, base_seed, seed_ptr,
-                                 out + (i64)t * out_track_stride, stream, dbg, nullptr, plan_hdr, plan_ent, !plan_made);
-        if (rc) return rc;
+                                 out + (i64)t * out_track_stride, stream, dbg, nullptr, plan_hdr, plan_ent, !plan_made, 0, list, list_count);
+        if (rc) break;
         plan_made = true;
     }
-    return GVL_OK;
+    if (list_mem) (void)hipFreeAsync(list_mem, s);
+    return rc;
 }
 
 int gvli::launch_track_plan(const TrackArgs &TA, int2 *hdr, i32x4 *ent, int chunks, i64 fixed_len, i64 rows_per_batch_q, void *stream) {
     const i64 wgrid = (TA.n_rows + 3) / 4;
-    track_plan_kernel<<<dim3((unsigned)wgrid), dim3(256), 0, (hipStream_t)stream>>>(TA, hdr, ent, chunks, fixed_len, rows_per_batch_q);
+    // (ragged rows of the epoch table: every batch has its own row offsets)
+    if (fixed_len < 0 && rows_per_batch_q > 0)
+        track_plan_kernel<true><<<dim3((unsigned)wgrid), dim3(256), 0, (hipStream_t)stream>>>(TA, hdr, ent, chunks, fixed_len, rows_per_batch_q);
+    else
+        track_plan_kernel<false><<<dim3((unsigned)wgrid), dim3(256), 0, (hipStream_t)stream>>>(TA, hdr, ent, chunks, fixed_len, rows_per_batch_q);
     return check_launch("gvl_loader_start_epoch(row plans)");
 }
 

@@ -607,3 +607,31 @@ def realign_tracks(dev: "HapsDevice", regions, shifts, geno_offset_idx, out_offs
                                               _stream_ptr()))
         out._keepalive = (bt, tr, to, qs)
         return out
+
+
+def tracks_batch(dev: "HapsDevice", regions, shifts, geno_offset_idx, offset_idxs, track_sets, params, strategy_id=0, base_seed=0,
+                 to_rc=None, *, output_length: int, out_offsets=None, max_row_len=None, scratch_stride: int) -> torch.Tensor:
+    """gvl_tracks_batch: every track of a batch painted from its intervals and realigned to every haplotype, in one call.
+    ``track_sets``: a ctypes array of ``GvlTrackSet``.  Fixed rows (``output_length >= 1``) -> f32 (T, b * P * L).  Ragged rows
+    (``output_length = -1``): ``out_offsets`` are the haplotype rows' (b * P + 1) offsets (``HapsDevice.hap_offsets``), ``max_row_len``
+    bounds a row (default: the longest) -> f32 (T, b * P * max_row_len), track t's row k at ``[t, out_offsets[k]:out_offsets[k + 1]]``."""
+    d = dev.device
+    with _on_device(d):
+        ragged = int(output_length) < 0
+        bt = dev.prepare_batch(regions, shifts, geno_offset_idx, -1 if ragged else int(output_length), None, None, to_rc,
+                               out_offsets if ragged else None, max_row_len=max_row_len if ragged else None)
+        b, P, T = int(bt.regions.shape[0]), int(bt.c.ploidy), len(track_sets)
+        L = max(int(bt.c.max_row_len), 1)
+        oi = _dev(offset_idxs, torch.int64, d)
+        K = b * P
+        out = torch.empty((T, K * L), dtype=torch.float32, device=d)
+        if b == 0 or T == 0:
+            return out
+        n_scr = int(dev.lib.gvl_tracks_scratch_bytes(C.c_int64(b), C.c_int64(P), C.c_int64(int(scratch_stride))))
+        scr = torch.empty(n_scr, dtype=torch.uint8, device=d)
+        p = (C.c_double * 1)(float(np.asarray(params, np.float64).ravel()[0]))
+        _lib.check(dev.lib.gvl_tracks_batch(C.byref(dev.c), C.byref(bt.c), _ptr(oi), track_sets, C.c_int32(T), p, C.c_int64(int(strategy_id)),
+                                            C.c_uint64(int(base_seed) & 0xFFFFFFFFFFFFFFFF), _ptr(out), C.c_int64(K * L), _ptr(scr),
+                                            C.c_int64(int(scratch_stride)), _stream_ptr()))
+        out._keepalive = (bt, oi, scr)
+        return out

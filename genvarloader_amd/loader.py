@@ -287,7 +287,8 @@ class DeviceHapsDataset:
 
 @dataclass
 class TrackBatch(Batch):
-    tracks: torch.Tensor | None = None     # (b, n_tracks, P, L) f32, realigned to each haplotype
+    tracks: torch.Tensor | None = None     # (b, n_tracks, P, L) f32, realigned to each haplotype; ragged: (n_tracks, total)
+    #                                        ((n_tracks, capacity) in the native ring: see DeviceHapsTracksDataset)
 
 
 class _EpochArrays:
@@ -354,13 +355,21 @@ class DeviceHapsTracksDataset(DeviceHapsDataset):
     ``len - min_p(min(diff, 0))`` (``_reconstruct.py:191``; computed on the device), then realign it to every
     haplotype with the insertion-fill strategy (``intervals_and_realign_track_fused``,
     ``src/ffi/mod.rs:2551-2672``); negative-strand rows are reversed.  No host sync per batch.
-    Batches own their memory (random access / custom samplers / ``DeviceLoader``'s Python loop)."""
+    Batches own their memory (random access / custom samplers / ``DeviceLoader``'s Python loop).
+
+    ``output_length=-1`` (the reference's default, ``_reconstruct.py:183-203``): ragged rows, every track row as long as its
+    haplotype.  ``batch.out_offsets`` ((b * P + 1,) i64) is shared by ``haps`` / ``onehot`` and the tracks: track ``t``, row ``k``
+    is ``batch.tracks[t, out_offsets[k]:out_offsets[k + 1]]``.  ``batch.tracks`` is (T, total) f32 from ``__getitem__`` and the
+    Python submit loop (one host read per batch for the total, as for ragged haplotypes), and (T, capacity) f32 in the native
+    ring, capacity = ``batch_size * P * max_row_len()`` (a short last batch too), with ``batch.sizes`` = {total, longest row} on
+    the device.  (The reference's combined (b, t, p) offsets are not reproduced: its buffer is track-major, one block per track,
+    and each block is what ``intervals_and_realign_track_fused`` writes over the haplotype offsets.)  ``annotate=True`` is refused."""
 
     def __init__(self, dev, regions, n_samples, ploidy, *, tracks: dict, strategy_id: int = 0, param: float = 0.0,
                  base_seed: int | None = None, **kw):
         super().__init__(dev, regions, n_samples, ploidy, **kw)
-        if self.ragged or self.annotate:
-            raise ValueError("DeviceHapsTracksDataset: fixed-length rows, no annotations")
+        if self.annotate:
+            raise ValueError("DeviceHapsTracksDataset: no annotations")
         from . import device as _device
 
         d = dev.device
@@ -467,8 +476,13 @@ class DeviceHapsTracksDataset(DeviceHapsDataset):
         b, P, L = int(base.idx.numel()), self.ploidy, self.output_length
         if b == 0 or not self._itv:
             return TrackBatch(base.onehot, base.haps, base.idx, base.regions, base.shifts, base.geno_offset_idx,
-                              base.to_rc, tracks=None)
+                              base.to_rc, base.out_offsets, tracks=None)
         K, T = b * P, len(self._itv)
+        total = None
+        if self.ragged:
+            # rows at the haplotypes' offsets; a row's bound for the launch, the batch's total from the haplotype buffer (its host read)
+            total = int(base.haps.numel()) if base.haps is not None else int(base.onehot.shape[0])
+            L = self.max_row_len()
         # ONE native call for the track half (gvl_tracks_batch): scratch-track lengths, then paint +
         # realign per track; output and scratch share one arena, no torch op per batch
         lib = dev.lib
@@ -477,8 +491,8 @@ class DeviceHapsTracksDataset(DeviceHapsDataset):
         arena = torch.empty(out_bytes + n_scr, dtype=torch.uint8, device=d)
         bt = GvlBatch(regions=base.regions.data_ptr(), regions_stride=4, shifts=base.shifts.data_ptr(),
                       geno_offset_idx=base.geno_offset_idx.data_ptr(), batch=b, ploidy=P, keep=None, keep_offsets=None,
-                      to_rc=None if base.to_rc is None else base.to_rc.data_ptr(), output_length=L, out_offsets=None,
-                      max_row_len=L)
+                      to_rc=None if base.to_rc is None else base.to_rc.data_ptr(), output_length=self.output_length,
+                      out_offsets=None if total is None else base.out_offsets.data_ptr(), max_row_len=L)
         par = (C.c_double * 1)(self.param)
         with _on_device(d):
             _lib.check(lib.gvl_tracks_batch(
@@ -486,9 +500,12 @@ class DeviceHapsTracksDataset(DeviceHapsDataset):
                 C.c_int64(self.strategy_id), C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), C.c_void_p(arena.data_ptr()),
                 C.c_int64(K * L), C.c_void_p(arena.data_ptr() + out_bytes), C.c_int64(self._stride),
                 C.c_void_p(torch.cuda.current_stream(d).cuda_stream)))
-        tracks = arena[:4 * T * K * L].view(torch.float32).view(T, b, P, L).permute(1, 0, 2, 3)
+        if total is None:
+            tracks = arena[:4 * T * K * L].view(torch.float32).view(T, b, P, L).permute(1, 0, 2, 3)
+        else:
+            tracks = arena[:4 * T * K * L].view(torch.float32).view(T, K * L)[:, :total]
         out = TrackBatch(base.onehot, base.haps, base.idx, base.regions, base.shifts, base.geno_offset_idx, base.to_rc,
-                         tracks=tracks)
+                         base.out_offsets, tracks=tracks)
         out._arena = base._arena
         out.base_seed = seed
         out._keep = (arena,)
@@ -789,6 +806,9 @@ class DeviceLoader:
             oo, sz = view(6, torch.int64, (K + 1,)), view(11, torch.int64, (2,))
             if ds.annotate:
                 av, ap = view(7, torch.int32, (cap,)), view(8, torch.int32, (cap,))
+            T = int(nat["cfg"].n_tracks)
+            if T:       # track t at t * batch_size * P * max_row_len, rows at out_offsets (a short last batch too)
+                tr = view(9, torch.float32, (T, self.batch_size * P * int(nat["cfg"].max_row_len)))
         else:
             oh = view(0, torch.uint8, (b, P, L, 4) if ds.layout == "lc" else (b, P, 4, L)) if ds.onehot else None
             hp = view(1, torch.uint8, (b, P, L)) if ds.haps else None

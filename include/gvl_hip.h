@@ -184,7 +184,7 @@ typedef struct gvl_out {
 
 int gvl_abi_version(void);
 /* Test / diagnostic switches (the bits of the GVL_DBG environment variable, see
- * enum DbgBit in csrc/gvl_internal.inc); flags < 0 returns to the environment's value. */
+ * enum DbgBit in csrc/gvl_internal.inc; the sign bit is one of them); flags == -1 returns to the environment's value. */
 int gvl_set_debug_flags(int flags);
 /* Launch-policy overrides, process-wide: for A/B measurements and for tests that must force a schedule the built-in policy
  * would not pick at their sizes.  value <= 0 returns the key to the built-in policy.  Results never depend on them.
@@ -454,8 +454,14 @@ int gvl_paint_tracks(const gvl_track_set *ts, const int64_t *offset_idxs, const 
  * scratch-track length per query = len - min_p(min(diff, 0)) (diff = get_diffs_sparse in query mode),
  * then per track: paint the query's intervals (list offset_idxs[q]) into its scratch track, realign it
  * to every haplotype (fill strategy / params / base_seed as gvl_realign_tracks), reverse negative-strand
- * rows.  bt: regions, shifts, geno_offset_idx, to_rc, batch, ploidy, output_length (fixed, >= 0).
- * out: f32, track t at out + t * out_track_stride, rows (batch * ploidy, output_length).
+ * rows.  bt: regions, shifts, geno_offset_idx, to_rc, batch, ploidy, output_length.
+ * Fixed rows (output_length >= 0): out f32, track t at out + t * out_track_stride, rows (batch * ploidy, output_length).
+ * Ragged rows (output_length == -1, the reference's default): bt->out_offsets = the haplotype rows' batch * ploidy + 1
+ * offsets (gvl_hap_offsets, or the native loop's), bt->max_row_len > 0 a bound on every row, and out_track_stride >=
+ * batch * ploidy * max_row_len; track t's row k is out[t * out_track_stride + out_offsets[k] .. + out_offsets[k + 1]), as long as
+ * haplotype k.  The caller's offsets are read, never written; the rows are clamped to that capacity (nothing is written past a
+ * track's batch * ploidy * max_row_len values), and a row longer than max_row_len or past the capacity is reported by
+ * gvl_async_error() and left partly unwritten.
  * scratch: gvl_tracks_scratch_bytes(batch, ploidy, scratch_stride) bytes of the caller's device memory,
  * 256-byte aligned; scratch_stride = values reserved per query's scratch track (>= 2 * the longest
  * region is always enough).  No allocation, no host synchronisation. */
@@ -527,7 +533,7 @@ typedef struct gvl_loader_config {
                                     to it and reported by gvl_async_error() -- choose a true bound (longest
                                     region + the largest sum of insertion lengths of any genotype slot) */
     const gvl_track_set *tracks; /* HOST array of n_tracks interval stores (copied); list index = dataset index.
-                                    Fixed-length rows only.  Per batch: gvl_tracks_batch into the slot */
+                                    Fixed or ragged rows, no annotations.  Per batch: gvl_tracks_batch into the slot */
     int32_t n_tracks;
     int32_t track_seed_mode;     /* 0: track_seed for every batch; 1: per batch like the reference
                                     (_reconstruct.py:215-222): deterministic -> xor of the batch's dataset
@@ -552,7 +558,8 @@ typedef struct gvl_loader_batch {
     int32_t *annot_v_idxs;       /* want_annot: i32 per base, laid out like haps */
     int32_t *annot_ref_pos;
     float *tracks;               /* n_tracks > 0: f32 (n_tracks, batch_size * ploidy, output_length) -- track t of
-                                    a short last batch still starts at t * batch_size * ploidy * output_length */
+                                    a short last batch still starts at t * batch_size * ploidy * output_length.
+                                    Ragged: track t at t * batch_size * ploidy * max_row_len, its rows at out_offsets */
     int64_t *sizes;              /* ragged: device i64[2] = {total bases of the batch, longest row} */
     const uint64_t *track_seed;  /* device: the base_seed this batch's FlankSample fills used (mode 1) */
 } gvl_loader_batch;
@@ -602,8 +609,9 @@ int gvl_loader_set_epoch(gvl_loader *ld, uint64_t epoch);
 /* Bytes of the epoch table for n queries and the offsets of its GVL_LOADER_TABLE_PARTS parts (regions i32
  * (n, 4), geno_offset_idx i64 (n, ploidy), shifts i32 (n, ploidy), to_rc u8 (n * ploidy), per-batch track
  * seeds u64 (ceil(n / batch_size)), and -- with tracks -- every batch's scratch-track offsets i64 (batch_size + 1
- * per batch), the k * output_length row offsets i64 (batch_size * ploidy + 1) the realignment reads and, for rows of several
- * 2048-value chunks, the rows' realignment plans (the row's entries, 2 KB per row, + 8 B per (row, chunk); left out when an
+ * per batch), the k * output_length row offsets i64 (batch_size * ploidy + 1) the realignment reads (unused for ragged rows, which
+ * share the haplotypes' offsets) and, for rows of several 2048-value chunks (ragged: a max_row_len of several; only when the
+ * epoch's ragged offsets below are in the table), the rows' realignment plans (the row's entries, 2 KB per row, + 8 B per (row, chunk); left out when an
  * epoch's would exceed gvl_set_tuning(GVL_TUNE_TRACK_PLAN_MAX_MB), default 512); and, last, for fixed-length rows of several
  * 2048-base chunks the haplotype kernel's chunk plans of every row (gvl_hap_plan_bytes; same cap: an epoch without them plans per
  * launch); and for ragged rows (output_length = -1) every batch's row offsets i64 (batch_size * ploidy + 1 per batch) and its
